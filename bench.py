@@ -11,6 +11,16 @@ device mailboxes over xGMI (stein_thinning/distributed.py PersistentShardedGreed
 the device exchange is unavailable): per-step kernels + RCCL all-gather of the rank records, the loop
 captured in a HIP graph.  The mode used is reported in config.parallelism.
 
+A plain run (`--gpus 1 --steps N --warmup W`) sets up, warms up, times the N thins and prints the line:
+metric / value / ms_per_step and the roofline of the timed launches.  `--dump-outputs DIR` also writes what
+the last timed thin returned (DIR/indices.npy, DIR/running_sums.npy, float64; the inputs are seeded, so two
+builds can be compared output for output).  Every other leg of the line -- cpu_baseline, the step-kernel
+timing, exact_arithmetic, near_tie_guard, dedup, end_to_end, and at N > 1 rank_hop, config5_sharded and
+chains_over_gpus -- takes runs of its own and is measured only under `--full` (null otherwise).  So is the
+whole `roofline` of a config without the persistent kernel (d > 8, config 5): it is the step kernel against
+HBM, built from the step-kernel timing.  `--full` belongs to the thin workload; the other workloads run as
+before (their CPU baselines on unless `--no-cpu-baseline`).
+
 Synthetic data (no network): the LV posterior chains of the reference live only in S3, so the
 "LV surrogate" is a seeded random-walk Metropolis chain on N(mu, Sigma) with mu, Sigma the
 reference's printed LV chain-0 moments (Gradient_free.ipynb cells 42-43), isotropic step 0.0052
@@ -538,6 +548,34 @@ def algorithmic_flop_per_pair(d: int, gf: bool) -> int:
     return 12 * d + 40 + (2 if gf else 0)
 
 
+DUMP_LIMIT_BYTES = 64 * 2 ** 20   # --dump-outputs: all files of one run together
+DUMP_SAMPLE_SEED = 20_240
+
+
+def dump_outputs(directory: str, arrays: dict) -> dict:
+    """--dump-outputs: write each array as <directory>/<name>.npy (float64; float32 inputs stay float32)
+    and return {name: shape written}.  When the arrays together exceed DUMP_LIMIT_BYTES, an array over its
+    equal share of the limit is cut to a fixed sample of its flattened elements (every stride-th position
+    from an offset drawn from DUMP_SAMPLE_SEED, so two runs with the same arguments keep the same elements
+    and the sample costs no more memory than what is kept)."""
+    os.makedirs(directory, exist_ok=True)
+    out = {k: np.ascontiguousarray(v, dtype=np.float32 if np.asarray(v).dtype == np.float32 else np.float64)
+           for k, v in arrays.items()}
+    if sum(v.nbytes for v in out.values()) > DUMP_LIMIT_BYTES:
+        share = DUMP_LIMIT_BYTES // len(out) - 4096   # the .npy header is part of the file
+        rng = np.random.default_rng(DUMP_SAMPLE_SEED)
+        for k in sorted(out):
+            v = out[k]
+            keep = share // v.itemsize
+            if v.size > keep:
+                stride = v.size // keep
+                start = int(rng.integers(stride))
+                out[k] = np.ascontiguousarray(v.reshape(-1)[start::stride][:keep])
+    for k, v in out.items():
+        np.save(os.path.join(directory, k + '.npy'), v)
+    return {k: list(v.shape) for k, v in out.items()}
+
+
 def _free_port() -> int:
     with socket.socket() as s:
         s.bind(('127.0.0.1', 0))
@@ -562,10 +600,18 @@ def main():
     ap.add_argument('--steps', type=int, default=5, help='timed thins')
     ap.add_argument('--warmup', type=int, default=2)
     ap.add_argument('--config', default='c4', choices=sorted(CONFIGS))
+    ap.add_argument('--full', action='store_true',
+                    help='thin workload: after the timed thins also run every other leg of the result line (CPU '
+                         'baselines, step-kernel timing, exact arithmetic, near-tie guard, dedup, end-to-end calls; '
+                         'N > 1: rank hop, config 5 sharded, chains over GPUs).  Without it those fields are null')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='thin workload: after the timed thins write what the last one returned as DIR/<name>.npy '
+                         '(float64): indices (the m selected rows) and, on one device, running_sums (the n sums A)')
     ap.add_argument('--cpu-steps', type=int, default=100, help='greedy steps of the NumPy one-core sample')
-    ap.add_argument('--no-cpu-baseline', action='store_true')
-    ap.add_argument('--no-kernel-timing', action='store_true')
-    ap.add_argument('--no-e2e', action='store_true', help='skip the end_to_end legs (drop-in thin on host arrays)')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='--full without the cpu_baseline leg')
+    ap.add_argument('--no-kernel-timing', action='store_true', help='--full without the step-kernel timing')
+    ap.add_argument('--no-e2e', action='store_true',
+                    help='--full without the end_to_end legs (drop-in thin on host arrays)')
     ap.add_argument('--no-graph', action='store_true', help='N > 1: eager per-step launches instead of a HIP graph')
     ap.add_argument('--sharded', action='store_true', help='use the sharded (RCCL) path even at N = 1')
     ap.add_argument('--no-config5', action='store_true',
@@ -601,6 +647,10 @@ def main():
     args = ap.parse_args()
     if args.gpus < 1:
         ap.error('--gpus must be >= 1')
+    if args.steps < 1:
+        ap.error('--steps must be >= 1')
+    if args.dump_outputs and args.workload != 'thin':
+        ap.error('--dump-outputs is implemented for the thin workload only')
     env_world = os.environ.get('WORLD_SIZE')
     if env_world is None and args.gpus > 1:
         return _launch_ranks(sys.argv[1:])
@@ -687,14 +737,24 @@ def main():
         result_idx = idx.cpu().numpy().view(np.uint32)
     else:
         result_idx = runner.indices() if hasattr(runner, 'indices') else runner.backend.indices()
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        # what the last timed thin returned (st_greedy's idx_out and a_work), before any --full leg reuses
+        # the buffers
+        outputs = {'indices': result_idx}
+        if not sharded:
+            outputs['running_sums'] = a[:n].cpu().numpy()
+        dumped = dump_outputs(args.dump_outputs, outputs)
+    # everything below the timed thins that takes runs of its own is measured under --full only
+    full = args.full
     # N > 1: the measured rank level of this run and config 5 sharded (nulls at N = 1)
     hop, c5 = None, config5_sharded(rank, 1, dev)
-    if sharded and world > 1 and runner.mode == 'device-exchange':
+    if full and sharded and world > 1 and runner.mode == 'device-exchange':
         hop = rank_hop(elapsed / args.steps * 1e3, integrand, m, rank, world, dev)
-    if sharded and world > 1 and not args.no_config5 and args.config == 'c4':
+    if full and sharded and world > 1 and not args.no_config5 and args.config == 'c4':
         c5 = config5_sharded(rank, world, dev)
     cog = chains_over_gpus(rank, 1, dev)
-    if sharded and world > 1 and not args.no_chains and args.config == 'c4':
+    if full and sharded and world > 1 and not args.no_chains and args.config == 'c4':
         _set_guard(None)   # the drop-in default (guard on unless ST_NEAR_TIE=0), as the reference's call gets it
         cog = chains_over_gpus(rank, world, dev)
         _set_guard(bool(args.headline_guard))
@@ -766,7 +826,7 @@ def main():
                                      'bytes, not the streaming design\'s n m (16 d + 16) B (SURVEY 8(d)), which '
                                      'would exceed HBM peak at this kernel time'},
             }
-        if not sharded and not args.no_kernel_timing:
+        if full and not sharded and not args.no_kernel_timing:
             s_avg, s_med = kernel_timing(prob, min(m, 200))
             step = {
                 'kernel': f'greedy_step_ct<{d}> (launch-per-step path, st_greedy_steps)' if d <= 8 else
@@ -786,10 +846,10 @@ def main():
                             'algorithmic_bytes_per_launch': step['algorithmic_bytes_per_launch'],
                             'bytes_per_pair': bytes_per_pair,
                             'timing': 'HIP events around back-to-back single-step launches'}
-        if world == 1 and not args.no_cpu_baseline:
+        if full and world == 1 and not args.no_cpu_baseline:
             cpu = cpu_baseline(cfg, integrand, args.cpu_steps, result_idx, arithmetic)
         exact = None
-        if world == 1 and not sharded and d <= 8 and arithmetic == 'compact':
+        if full and world == 1 and not sharded and d <= 8 and arithmetic == 'compact':
             # the same thin with the exact arithmetic (NumPy's evaluation order; not `value`): its
             # time and whether it selects the same indices as the timed compact run
             import stein_thinning
@@ -811,7 +871,7 @@ def main():
                 torch.cuda.synchronize()
         guarded = None
         guard_lib = _set_guard(None)   # the drop-in default from here on (ST_NEAR_TIE, on unless '0')
-        if world == 1 and not sharded and d in (2, 4) and arithmetic == 'compact' and nat.near_tie_guard() \
+        if full and world == 1 and not sharded and d in (2, 4) and arithmetic == 'compact' and nat.near_tie_guard() \
                 and guard_lib:
             # the same thin of all n rows with the near-tie guard (not `value`): its time and first
             # flagged step (-1 none; rows that repeat their predecessor tie exactly, so a raw MCMC sample
@@ -834,10 +894,10 @@ def main():
                        'note': 'st_greedy of all n rows with the near-tie guard (DESIGN.md section 1); a flagged '
                                'drop-in thin is re-run in the exact arithmetic ("exact_arithmetic")'}
         dedup = None
-        if world == 1 and not sharded:
+        if full and world == 1 and not sharded:
             dedup = dedup_timing(prob, m, result_idx, stream)
         e2e = None
-        if world == 1 and not cfg['gf'] and not cfg.get('d50') and not args.no_e2e:
+        if full and world == 1 and not cfg['gf'] and not cfg.get('d50') and not args.no_e2e:
             # the drop-in call on host arrays (not `value`): standardisation + 'med' + H2D upload +
             # SoA layout + the persistent launch + D2H of the indices
             from stein_thinning import thinning as st
@@ -918,6 +978,8 @@ def main():
                                    'thin(sample, gradient, m) on host NumPy arrays (validation, standardisation, '
                                    'med, H2D, dedup, launch, D2H), the median of three calls after the timed region'},
                        'first_indices': result_idx[:8].tolist()},
+            'full': bool(full),
+            'outputs': {'dir': args.dump_outputs, 'shapes': dumped} if dumped else None,
             'exchange': exchange,
             'degraded': degraded,
             'rank_hop': hop,

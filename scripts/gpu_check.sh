@@ -30,7 +30,7 @@ if [[ $MODE == files ]]; then   # gpu_check.sh files <pytest args...>
   step pytest_files 1100 python -u -m pytest -m gpu -x -q --timeout 300 --timeout-method thread "$@"
 fi
 if [[ $MODE == all || $MODE == bench ]]; then
-  step bench 900 python bench.py --steps 3 --warmup 1
+  step bench 900 python bench.py --full --steps 3 --warmup 1
 fi
 if [[ $MODE == all || $MODE == prof ]]; then
   step rocprof 900 rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/prof -o run -- python3 bench.py --steps 2 --warmup 1 --no-cpu-baseline

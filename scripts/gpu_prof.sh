@@ -21,7 +21,7 @@ run() {   # run <name> <timeout_s> <cmd...>
   [[ $rc == 0 ]] || exit $rc
 }
 if [[ $MODE == full ]]; then
-  run bench_$CFG 600 python3 bench.py --config $CFG --steps 5 --warmup 2 "${EXTRA[@]}"
+  run bench_$CFG 600 python3 bench.py --full --config $CFG --steps 5 --warmup 2 "${EXTRA[@]}"
 fi
 if [[ $MODE == full || $MODE == trace ]]; then
   run trace_$CFG 600 rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/prof_$CFG -o trace -- \

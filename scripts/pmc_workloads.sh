@@ -12,7 +12,7 @@ export TMPDIR=/tmp
 declare -A ARGS=( [energy]="--workload energy" [ksd_c2]="--workload ksd" [proxy_gauss]="--workload proxy"
                   [proxy_t]="--workload proxy --proxy-kind t" [lv]="--workload lv"
                   [c4_persistent]="--config c4 --no-kernel-timing" [lv2]="--workload lv"
-                  [chains_batch]="--workload chains" [c4_dropin]="--config c4 --no-kernel-timing" )
+                  [chains_batch]="--workload chains" [c4_dropin]="--full --config c4 --no-kernel-timing" )
 declare -A KERN=( [energy]="dist_colsum_kernel" [ksd_c2]="ksd_colsum_kernel" [proxy_gauss]="proxy_mfma_buf_kernel"
                   [proxy_t]="proxy_mfma_buf_kernel" [lv]="lv_kernel<10>"
                   [c4_persistent]="greedy_persistent<4, false, 9, 512, 1, true, false, st::PersistArgs, false>" [lv2]="lv_dense_kernel"

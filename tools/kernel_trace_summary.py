@@ -1,7 +1,7 @@
 """Median duration of one kernel's TIMED dispatches from a rocprofv3 --kernel-trace CSV.
 
 bench.py enqueues, per kernel of interest, `warmup` untimed dispatches, then `steps` timed ones
-(then, for the thin workload, the end-to-end drop-in calls).  This picks dispatches
+(then, for the thin workload under --full, the other legs and the end-to-end drop-in calls).  This picks dispatches
 [warmup, warmup + steps) of the kernels whose name contains `--kernel` (in dispatch order) and
 prints their median / mean / min / max, so the bench line's `kernel_median_us` can be checked
 against the profiler's own clock:
