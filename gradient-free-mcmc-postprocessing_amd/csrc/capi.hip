@@ -106,7 +106,7 @@ int st_tune(int32_t key, int32_t value) {
 
 int32_t st_tune_get(int32_t key) {
     const bool persist = (key >= 3 && key <= 5) || key == 8 || key == 9 || key == 10 || key == 12 || key == 15 ||
-                         key == 16 || key == 19 || key == 23;
+                         key == 16 || key == 19 || key == 23 || (key >= 100 && key <= 110);
     return persist ? st::persistent_tune_get(key) : st::tune_get(key);
 }
 

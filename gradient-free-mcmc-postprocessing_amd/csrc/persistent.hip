@@ -83,9 +83,31 @@ static uint64_t* g_stamps = nullptr;
 #ifdef ST_PERSIST_STAMPS
 extern "C" int st_debug_set_stamps(uint64_t* buf) { g_stamps = buf; return 0; }
 #endif
+// st_tune_get keys 100 .. 110 (read-only): the last plan the calling host thread made for a launch of one
+// thin (plan_persistent; not the eligibility query, not a batch) -- every field -1 before the thread has
+// planned anything
+namespace {
+struct LastPlan {
+    int G = -1, R = -1, use_cmp = -1, guard = -1;   // blocks, rows per block, compact-only kernel first, GUARD kernels
+    int nt = -1, rt = -1, RL = -1, sal = -1;        // the kernel that runs first: threads, register rows, LDS rows, key 15
+    int rt_g = -1, RL_g = -1, sal_g = -1;           // the (gated) general kernel
+};
+}  // namespace
+static thread_local LastPlan t_last_plan;
 // the current value of a persistent-kernel st_tune key (st_tune_get); INT32_MIN for other keys
 int persistent_tune_get(int key) {
     switch (key) {
+        case 100: return t_last_plan.G;
+        case 101: return t_last_plan.R;
+        case 102: return t_last_plan.use_cmp;
+        case 103: return t_last_plan.guard;
+        case 104: return t_last_plan.nt;
+        case 105: return t_last_plan.rt;
+        case 106: return t_last_plan.RL;
+        case 107: return t_last_plan.sal;
+        case 108: return t_last_plan.rt_g;
+        case 109: return t_last_plan.RL_g;
+        case 110: return t_last_plan.sal_g;
         case 3: return g_persist_rt;
         case 4: return g_persist_nt;
         case 5: return g_persist_grid;
@@ -456,6 +478,13 @@ static hipError_t plan_persistent(const double* x, const double* g, const double
     P.lds = lds; P.lds_c = lds_c;
     P.region = region;
     P.ws = p;
+    // (not a batch's per-chain plans: launch_greedy_persistent_batch may plan a chain again with the batch's
+    // common register rows, and launches one grid for all of them)
+    const PersistArgs& first = use_cmp ? ac : a;
+    if (!batch)
+        t_last_plan = LastPlan{G, (int)R, use_cmp ? 1 : 0, guard ? 1 : 0,
+                               use_cmp ? 512 : nt, use_cmp ? rt_c : rt, first.RL, first.stream_a_lds,
+                               rt, a.RL, a.stream_a_lds};
     return hipSuccess;
 }
 

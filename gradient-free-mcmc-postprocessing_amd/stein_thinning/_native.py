@@ -9,6 +9,7 @@ raises if the extension or a HIP device is missing.
 """
 from __future__ import annotations
 
+import collections
 import ctypes
 import os
 import threading
@@ -262,6 +263,23 @@ def near_tie_step(ws) -> int:
     check(lib().st_greedy_near_tie(ptr(ws), ws.numel() * ws.element_size(), ctypes.byref(out), stream_handle()),
           'st_greedy_near_tie')
     return int(out.value)
+
+
+class LastPlan(collections.namedtuple('LastPlan', [
+        'blocks', 'rows_per_block', 'compact_first', 'guarded', 'threads', 'reg_rows', 'lds_rows', 'stream_a_lds',
+        'gen_reg_rows', 'gen_lds_rows', 'gen_stream_a_lds'])):
+    """The persistent-kernel plan the library last made on this host thread (st_tune_get keys 100 .. 110):
+    grid and rows per block, whether the compact-only kernel runs first and whether the GUARD kernels were
+    chosen; threads per block, register rows per thread, LDS rows and stream_a_lds of the kernel that runs
+    first; register rows, LDS rows and stream_a_lds of the (gated) general kernel.  Every field is -1
+    before the thread has planned a launch; a batch launch (thin_chains) leaves the record as it was."""
+    __slots__ = ()
+
+
+def last_plan() -> LastPlan:
+    """Read-only: the plan of this host thread's last persistent launch (``LastPlan``)."""
+    L = lib()
+    return LastPlan(*(int(L.st_tune_get(100 + k)) for k in range(len(LastPlan._fields))))
 
 
 def check_host(rc: int, what: str = '') -> None:

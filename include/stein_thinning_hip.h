@@ -100,7 +100,16 @@ int64_t st_greedy_workspace_bytes(int64_t n, int32_t d, int32_t nranks);
 int st_tune(int32_t key, int32_t value);
 
 /* the current value of a greedy-kernel st_tune key (0 .. 6, 8 .. 12, 15, 16, 19, 20, 22, 23; -1 = automatic);
- * INT32_MIN for other keys (save / restore around a temporary setting) */
+ * INT32_MIN for other keys (save / restore around a temporary setting).
+ * Keys 100 .. 110 are read-only (st_tune rejects them): the persistent-kernel plan the CALLING HOST THREAD
+ * last made for a launch of one thin (st_greedy / st_greedy_sharded; not the eligibility query
+ * st_greedy_sharded_supported, and not st_greedy_batch, whose chains share one grid), every one -1 before the thread has planned anything -- 100 = blocks,
+ * 101 = rows per block, 102 = 1 if the compact-only kernel runs first (the general kernel gated behind
+ * it), 103 = 1 if the near-tie GUARD kernels were chosen; of the kernel that runs first: 104 = threads per
+ * block, 105 = register rows per thread, 106 = LDS rows per block, 107 = 1 if the streamed rows' sums live
+ * in LDS (key 15's decision); of the general kernel (the same kernel when 102 = 0): 108 = register rows,
+ * 109 = LDS rows, 110 = streamed sums in LDS.  Rows of a block, by offset: register rows
+ * [0, register rows x threads), then the LDS rows, then the streamed rows up to rows per block. */
 int32_t st_tune_get(int32_t key);
 
 /* doubles per rank-candidate record {value, global index bits, x[d], g[d], w} (even) */

@@ -1,6 +1,8 @@
 """NumPy restatement of stein_thinning.diagnostics.greedy_margins over the C bit model (test
 infrastructure): per step, the running sums A of the bit model (oracle/stein_ref.c, the kernels'
-arithmetic) -> winner, runner-up, margin in ulps, and the error band of the module's definition."""
+arithmetic) -> winner, runner-up, margin in ulps, and the error band of the module's definition.
+Also near_tie_twins, the near-tie construction of the guard tests (twins appended to a small sample);
+tests/planted_ref.py plants pairs at chosen rows."""
 import numpy as np
 
 from stein_thinning.diagnostics import BAND_ULPS_PER_TERM

@@ -439,3 +439,71 @@ def test_near_tie_guard_across_processes(tmp_path, world):
         idx, tie, _ = res[r]['mirror']
         np.testing.assert_array_equal(np.asarray(idx, dtype=np.uint32), o.thin(Z, -Z, 3, standardize=False))
         assert tie == 0
+
+
+def _near_tie_plans_worker(rank, world, port, out_dir):
+    """One of two ranks on the one GPU, 4 blocks each (st_tune key 5): the base sample for one step, then the
+    planted samples the parent saved, through thin_sharded; reports indices, verdict, engine and the plan this
+    rank's launcher made last."""
+    os.environ.update(MASTER_ADDR='127.0.0.1', MASTER_PORT=str(port), ST_SHARDED_EXCHANGE='device')
+    torch.cuda.set_device(0)
+    dist.init_process_group('gloo', rank=rank, world_size=world)
+    try:
+        import json
+        from tests import planted_ref as pl
+        from stein_thinning import _native as nat
+        from stein_thinning import distributed as sd
+        L = nat.lib()
+        prev = int(L.st_tune_get(5))
+        assert L.st_tune(5, pl.RANK_KEY5) == 0
+        try:
+            out = {}
+            data = np.load(os.path.join(out_dir, 'cases.npz'))
+            for name in ['base'] + list(pl.RANK_CASES):
+                a = sd.thin_sharded(data[f'{name}_x'], data[f'{name}_g'], 1 if name == 'base' else 20)
+                out[name] = (a.tolist(), sd.last_near_tie, sd.last_mode, list(nat.last_plan()))
+        finally:
+            L.st_tune(5, prev)
+        with open(os.path.join(out_dir, f'ntp{rank}.json'), 'w') as f:
+            json.dump(out, f)
+    finally:
+        dist.destroy_process_group()
+
+
+def test_near_tie_plans_across_two_processes(tmp_path):
+    """The guarded general kernel of a multi-rank thin at 9 000 rows per block (512 threads, 4 register rows, LDS
+    rows, streamed rows; the earlier multi-rank guard test runs ~400 rows: one block per rank of the 256-thread
+    one-row kernel): a twin whose runner-up sits in an LDS row and one in the last streamed row of rank 1, and a
+    bitwise copy of the winner in the other rank -- NumPy's indices and the model's verdict on every rank.
+    The plan is read after each thin.  The base sample and the copy flag nothing, so their last launch is the
+    guarded one and last_plan() shows it: the GUARD general kernel of 512 threads, 4 register rows, LDS and
+    streamed rows.  A flagged twin's last launch is its re-run in the exact arithmetic, which overwrites the
+    record (same grid, unguarded), so the guarded plan of the twins is not observed but follows from the base
+    and copy runs: planning depends on n, d and the knobs only, and all four samples share them."""
+    import json
+    from tests import planted_ref as pl
+    from stein_thinning import _native as nat
+    world = 2
+    cases = {name: pl.rank_case(name) for name in pl.RANK_CASES}
+    Xb, Gb, _ = pl.planted_base(2, pl.RANK_N, pl.OTHER_SEED)
+    arrays = {'base_x': Xb, 'base_g': Gb}
+    for name, case in cases.items():
+        case.check_preconditions()
+        arrays[f'{name}_x'], arrays[f'{name}_g'] = case.x, case.g
+    np.savez(tmp_path / 'cases.npz', **arrays)
+    mp.spawn(_near_tie_plans_worker, args=(world, _free_port(), str(tmp_path)), nprocs=world, join=True)
+    res = [json.loads((tmp_path / f'ntp{r}.json').read_text()) for r in range(world)]
+    for r in range(world):
+        for name in ('base', 'copy_other_rank'):   # unflagged: the guarded compact run is the last launch
+            lp = nat.LastPlan(*res[r][name][3])
+            assert (lp.blocks, lp.rows_per_block, lp.guarded, lp.compact_first, lp.threads, lp.reg_rows) == \
+                (pl.RANK_KEY5, 9000, 1, 0, 512, 4), (r, name, lp)
+            layout = pl.block_layout(lp.rows_per_block, lp.reg_rows, lp.lds_rows, lp.threads)
+            assert layout == pl.RANK_LAYOUT and 0 < layout[0] < layout[1] < layout[2]   # LDS and streamed rows exist
+        for name, case in cases.items():
+            idx, tie, mode, plan = res[r][name]
+            np.testing.assert_array_equal(np.asarray(idx, dtype=np.uint32), case.want, err_msg=f'{name} rank {r}')
+            assert tie == case.first == (-1 if case.kind == 'copy' else 8), (name, r, tie)
+            assert mode == 'device-exchange'
+            # (a flagged thin's last launch is its re-run in the exact arithmetic: same grid, no guard)
+            assert plan[:2] == [pl.RANK_KEY5, 9000] and plan[3] == (1 if case.first < 0 else 0), (name, r, plan)

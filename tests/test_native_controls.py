@@ -57,3 +57,24 @@ def test_arithmetic_override_nests():
             assert nat.arithmetic() == 'compact' and int(nat.lib().st_tune_get(22)) == 1
         assert nat.arithmetic() == 'exact' and int(nat.lib().st_tune_get(22)) == 0
     assert int(nat.lib().st_tune_get(22)) == -1
+
+
+def test_last_plan_query_is_read_only_and_per_thread():
+    """st_tune_get keys 100 .. 110 (the plan this host thread last made, _native.last_plan): -1 on a thread
+    that has planned nothing, rejected by st_tune, and the keys around them still unknown."""
+    import threading
+    seen = {}
+
+    def worker():
+        L = nat.lib()
+        seen['plan'] = nat.last_plan()
+        seen['set'] = [int(L.st_tune(k, 1)) for k in range(100, 111)]
+        seen['after'] = nat.last_plan()
+        seen['unknown'] = [int(L.st_tune_get(k)) for k in (99, 111, 999)]
+    t = threading.Thread(target=worker)
+    t.start()
+    t.join()
+    assert len(nat.LastPlan._fields) == 11
+    assert tuple(seen['plan']) == (-1,) * 11 and seen['after'] == seen['plan']
+    assert seen['set'] == [nat.ST_ERR_INVALID] * 11
+    assert seen['unknown'] == [-2 ** 31] * 3

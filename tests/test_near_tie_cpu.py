@@ -11,6 +11,7 @@ from oracle import models
 from oracle import stein_numpy as o
 from oracle import stein_ref_c as oc
 from tests import margins_ref as mr
+from tests import planted_ref as pl
 from stein_thinning import thinning as st
 
 
@@ -149,3 +150,87 @@ def test_exact_tie_between_different_rows_flags():
     integrand = st._make_stein_integrand(X, -X, standardize=False)
     idx, _, gap, thr, flagged = _ties(integrand, 3)
     assert idx[0] == 3 and gap[0] == 0.0 and flagged[0]
+
+
+# ---- the planted pairs of tests/test_gpu_near_tie_plans.py, proved through the models at the nominal layouts ----
+
+def _check_planted(case):
+    """The construction's preconditions, and what the guard then promises: an unflagged thin already equals
+    the NumPy path, a flagged thin's re-run in the exact arithmetic does."""
+    case.check_preconditions()
+    if case.first < 0:
+        np.testing.assert_array_equal(case.idx, case.want)
+    exact, *_ = _ties(case.integrand, case.m, 'exact')
+    np.testing.assert_array_equal(exact, case.want)
+
+
+@pytest.mark.parametrize('d,position', pl.large_twin_cases())
+def test_planted_twins_large_plan(d, position):
+    """A twin at every row-class position of the large plan: the planted pair flags first exactly at step 8
+    with the selected row at winner_at, under both settings of st_tune key 15 (whose layouts differ in the
+    number of LDS rows)."""
+    for key15 in (-1, 0):
+        case = pl.planted_case('large', 'twin', d, position, key15=key15)
+        layout = pl.nominal_layout('large', d, key15)
+        want = pl.CLASSES[position]
+        assert (pl.row_class(layout, case.winner_at)[1], pl.row_class(layout, case.other_at)[1]) == want
+        assert pl.row_class(layout, case.winner_at)[0] == 1
+        assert pl.row_class(layout, case.other_at)[0] == (2 if position.startswith('xblock') else 1)
+        _check_planted(case)
+
+
+@pytest.mark.parametrize('plan,kind,d,position', pl.reduced_cases())
+def test_planted_pairs_every_plan(plan, kind, d, position):
+    case = pl.planted_case(plan, kind, d, position)
+    layout = pl.nominal_layout(plan, d)
+    want = (pl.REPEAT_CLASSES if kind == 'repeat' else pl.CLASSES)[position]
+    assert (pl.row_class(layout, case.winner_at)[1], pl.row_class(layout, case.other_at)[1]) == want
+    if plan in ('long', 'hbm') and position == 'block_last':   # a streamed visit past the 32 of the bit mask
+        assert case.other_at % layout[2] - layout[1] >= 32 * 448
+    _check_planted(case)
+
+
+@pytest.mark.parametrize('position', pl.MIRROR_REPEATS)
+def test_planted_mirror_among_repeats(position):
+    """The exact tie between different rows with every other LDS row of the block a repeat of its predecessor:
+    still flagged at step 0 (the repeats are duplicates of rows far from the origin)."""
+    case = pl.mirror_repeats_case(position)
+    it = case.integrand
+    rep = np.all(it.sample[1:] == it.sample[:-1], axis=1)
+    layout = pl.nominal_layout('large', 2)
+    lo, hi = layout[2] + layout[0], layout[2] + layout[1]
+    assert not rep[case.other_at - 1] and rep[lo:hi - 1].sum() >= hi - lo - 4
+    _check_planted(case)
+
+
+@pytest.mark.parametrize('kind,position,seed,weight_ulp', pl.GF_CASES)
+def test_planted_gradient_free_pairs(kind, position, seed, weight_ulp):
+    case = pl.planted_gf_case(kind, position, seed, weight_ulp)
+    w = case.integrand.weights
+    if kind == 'copy':
+        assert (w[case.winner_at] != w[case.other_at]) == weight_ulp
+    _check_planted(case)
+
+
+@pytest.mark.parametrize('plan,d', [(p, d) for p in pl.PLANS for d in (2, 4)])
+def test_planted_base_samples_flag_nothing(plan, d):
+    X, G, _ = pl.planted_base(d, pl.PLANS[plan]['n'], pl.OTHER_SEED)
+    assert not _ties(st._make_stein_integrand(X, G), 20)[4].any()
+
+
+def test_some_planted_twins_need_the_exact_rerun():
+    """Per d, at least one twin of the large plan on which the compact arithmetic departs from NumPy."""
+    for d, position in [(2, 'lds32'), (4, 'lds64')]:
+        case = pl.planted_case('large', 'twin', d, position)
+        assert not np.array_equal(case.idx, case.want)
+
+
+@pytest.mark.parametrize('name', list(pl.RANK_CASES))
+def test_planted_pairs_two_ranks(name):
+    """The pairs of the two-rank GPU case (tests/test_gpu_multiprocess.py): both rows of a twin in rank 1's
+    second block, a copy in rank 0."""
+    case = pl.rank_case(name)
+    kind, position, _, blk, oblk = pl.RANK_CASES[name]
+    assert (pl.row_class(pl.RANK_LAYOUT, case.winner_at), pl.row_class(pl.RANK_LAYOUT, case.other_at)) == \
+        ((blk, pl.CLASSES[position][0]), (oblk, pl.CLASSES[position][1]))
+    _check_planted(case)
