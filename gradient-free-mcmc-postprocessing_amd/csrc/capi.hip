@@ -51,6 +51,15 @@ int check_problem(const double* x, const double* g, const double* w, int64_t n, 
     return ST_OK;
 }
 
+// dense preconditioner: after check_problem -- d within the dense kernels' widths, the (d, d) array given
+int check_dense(const double* linv, int32_t d) {
+    if (d > st::kMaxDenseDim)
+        return fail(ST_ERR_UNSUPPORTED, "d = %d exceeds the dense-preconditioner maximum %d", d, st::kMaxDenseDim);
+    if (!linv) return fail(ST_ERR_INVALID, "linv pointer is NULL");
+    if (!aligned16(linv)) return fail(ST_ERR_INVALID, "linv must be 16-byte aligned");
+    return ST_OK;
+}
+
 // workspace layout: [control block (persistent kernel counters/status)][two ping-pong banks of
 // per-block candidate records, kMaxBlocks x stride doubles each]
 int64_t greedy_ws_bytes(int32_t d) {
@@ -175,6 +184,46 @@ int st_greedy(const double* x_soa, const double* g_soa, const double* weights, i
     if (pe != hipErrorNotSupported) (void)hipGetLastError();   // clear a failed launch
     return st_greedy_steps(x_soa, g_soa, weights, n, d, ld, linv_scale, linv_trace, 0, n_points,
                            n_points, idx_out, a_work, workspace, workspace_bytes, stream);
+}
+
+int st_greedy_dense(const double* x_soa, const double* g_soa, const double* weights, int64_t n,
+                    int32_t d, int64_t ld, const double* linv, double linv_trace, int64_t n_points,
+                    uint32_t* idx_out, double* a_work, void* workspace, int64_t workspace_bytes,
+                    void* stream) {
+    if (n_points < 1) return fail(ST_ERR_INVALID, "n_points must be >= 1");
+    int rc = check_problem(x_soa, g_soa, weights, n, d, ld);
+    if (rc) return rc;
+    rc = check_dense(linv, d);
+    if (rc) return rc;
+    if (!idx_out || !a_work || !workspace) return fail(ST_ERR_INVALID, "NULL output/workspace");
+    if (!aligned16(a_work) || !aligned16(workspace))
+        return fail(ST_ERR_INVALID, "a_work/workspace must be 16-byte aligned");
+    if (workspace_bytes < greedy_ws_bytes(d))
+        return fail(ST_ERR_INVALID, "workspace too small (%lld < %lld)", (long long)workspace_bytes,
+                    (long long)greedy_ws_bytes(d));
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    st::GreedyArgs a = make_args(x_soa, g_soa, weights, n, d, ld, 0.0, linv_trace, a_work);
+    a.compact = 0;   // one dense arithmetic; the diagonal is the exact one's
+    a.linv = linv;
+    a.idx_out = idx_out;
+    const int blocks = st::greedy_dense_blocks(n, d);
+    // a run starts: no near-tie word of an earlier run may survive (dense runs are unguarded: -2)
+    rc = hip_check(hipMemsetAsync(static_cast<char*>(workspace) + st::kWsTieOff, 0,
+                                  (size_t)(st::kWsBoundsOff + 40 - st::kWsTieOff), s),
+                   "near-tie words reset");
+    if (rc) return rc;
+    for (int64_t t = 0; t < n_points; ++t) {
+        a.t = t;
+        a.recs_in = bank(workspace, d, (int)((t + 1) & 1));
+        a.nrecs_in = blocks;
+        a.recs_out = bank(workspace, d, (int)(t & 1));
+        rc = hip_check(t == 0 ? st::launch_greedy_step(a, true, blocks, s) : st::launch_greedy_step_dense(a, blocks, s),
+                       "dense greedy step launch");
+        if (rc) return rc;
+    }
+    return hip_check(st::launch_greedy_finalize(bank(workspace, d, (int)((n_points - 1) & 1)), blocks,
+                                                a.rec_stride, idx_out, n_points - 1, s),
+                     "greedy finalize launch");
 }
 
 int st_greedy_near_tie(const void* workspace, int64_t workspace_bytes, int64_t* step_out, void* stream) {
@@ -687,6 +736,69 @@ int st_kmat(const double* x_soa, const double* g_soa, const double* weights, int
     st::PairArgs p{x_soa, g_soa, weights, ld, d, linv_scale, linv_trace};
     return hip_check(st::launch_kmat(p, nullptr, k, kmat_out, static_cast<hipStream_t>(stream)),
                      "kmat launch");
+}
+
+int st_kernel_pairs_dense(const double* x_soa, const double* g_soa, const double* weights, int64_t ld,
+                          int32_t d, const double* linv, double linv_trace, const int64_t* i1,
+                          const int64_t* i2, int64_t n_pairs, double* out, void* stream) {
+    if (n_pairs == 0) return ST_OK;
+    if (!x_soa || !g_soa) return fail(ST_ERR_INVALID, "sample/gradient pointer is NULL");
+    if (d < 1) return fail(ST_ERR_INVALID, "d must be >= 1 (got %d)", d);
+    int rc = check_dense(linv, d);
+    if (rc) return rc;
+    if (ld < 1) return fail(ST_ERR_INVALID, "ld must be >= 1");
+    if (n_pairs < 0 || !i1 || !i2 || !out) return fail(ST_ERR_INVALID, "bad pair list");
+    st::PairArgs p{x_soa, g_soa, weights, ld, d, 0.0, linv_trace, linv};
+    return hip_check(st::launch_pairs(p, i1, i2, n_pairs, out, static_cast<hipStream_t>(stream)),
+                     "dense pairs launch");
+}
+
+int st_ksd_colsum_dense(const double* x_soa, const double* g_soa, const double* weights, int64_t n,
+                        int64_t ld, int32_t d, const double* linv, double linv_trace, int64_t row_begin,
+                        int64_t row_end, double* csum_out, void* stream) {
+    int rc = check_problem(x_soa, g_soa, weights, n, d, ld);
+    if (rc) return rc;
+    rc = check_dense(linv, d);
+    if (rc) return rc;
+    if (!csum_out) return fail(ST_ERR_INVALID, "NULL output");
+    if (row_begin < 0 || row_end < row_begin || row_end > n)
+        return fail(ST_ERR_INVALID, "need 0 <= row_begin <= row_end <= n");
+    st::PairArgs p{x_soa, g_soa, weights, ld, d, 0.0, linv_trace, linv};
+    return hip_check(st::launch_ksd_colsum(p, n, row_begin, row_end, csum_out,
+                                           static_cast<hipStream_t>(stream)),
+                     "dense ksd column-sum launch");
+}
+
+int st_ksd_cumulative_dense(const double* x_soa, const double* g_soa, const double* weights, int64_t m,
+                            int64_t ld, int32_t d, const double* linv, double linv_trace, double* ks_out,
+                            void* workspace, int64_t workspace_bytes, void* stream) {
+    int rc = check_problem(x_soa, g_soa, weights, m, d, ld);
+    if (rc) return rc;
+    rc = check_dense(linv, d);
+    if (rc) return rc;
+    if (!ks_out || !workspace) return fail(ST_ERR_INVALID, "NULL output/workspace");
+    if (workspace_bytes < st_ksd_workspace_bytes(m, ld))
+        return fail(ST_ERR_INVALID, "workspace too small");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    st::PairArgs p{x_soa, g_soa, weights, ld, d, 0.0, linv_trace, linv};
+    double* csum = static_cast<double*>(workspace);
+    rc = hip_check(st::launch_ksd_colsum(p, m, 0, m, csum, s), "dense ksd column-sum launch");
+    if (rc) return rc;
+    // the finish reads the diagonal only: k(x, x) depends on tr, not on L
+    return hip_check(st::launch_ksd_finish(p, m, csum, ks_out, s), "ksd finish launch");
+}
+
+int st_kmat_dense(const double* x_soa, const double* g_soa, const double* weights, int64_t k, int64_t ld,
+                  int32_t d, const double* linv, double linv_trace, double* kmat_out, void* stream) {
+    int rc = check_problem(x_soa, g_soa, weights, k, d, ld);
+    if (rc) return rc;
+    rc = check_dense(linv, d);
+    if (rc) return rc;
+    if (!kmat_out) return fail(ST_ERR_INVALID, "NULL output");
+    if ((k + 63) / 64 > 65535) return fail(ST_ERR_UNSUPPORTED, "k too large for the tiled grid");
+    st::PairArgs p{x_soa, g_soa, weights, ld, d, 0.0, linv_trace, linv};
+    return hip_check(st::launch_kmat(p, nullptr, k, kmat_out, static_cast<hipStream_t>(stream)),
+                     "dense kmat launch");
 }
 
 int st_layout_soa(const double* rowmajor, int64_t n, int32_t d, int64_t ld, double* soa,

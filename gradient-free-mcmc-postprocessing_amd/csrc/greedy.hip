@@ -18,6 +18,7 @@
 // The kernel boundary is the only hand-off (no tickets, no last-block epilogue).
 #include "stein_math.hpp"
 #include "stein_internal.hpp"
+#include "stein_dense.hpp"
 
 namespace st {
 
@@ -303,6 +304,79 @@ __global__ __launch_bounds__(kBlock, 4) void greedy_step_rt(GreedyArgs a) {
     write_block_record(a, best_v, best_i, s_v, s_i);
 }
 
+// ------------------------------------------------------------------------------------------
+// Dense preconditioner (a.linv: Gamma^-1 = L, symmetric positive definite; stein_dense.hpp): the same
+// head, tail and record format as greedy_step_ct, the pair value by pair_dense.  D = d for d <= 8
+// (CPT adjacent candidates per lane); D = 16 for d = 9 .. 16: rows zero-padded in registers, L
+// zero-padded in LDS, one candidate per lane.  Step 0 is the isotropic diagonal kernel (k(x, x)
+// depends on tr only).  No inter-workgroup wait: the kernel boundary is the only hand-off.
+// ------------------------------------------------------------------------------------------
+template <int D, bool GF, int CPT>
+__global__ __launch_bounds__(kBlock) void greedy_step_dense(GreedyArgs a) {
+    constexpr bool CT = D <= kMaxCtDim;
+    static_assert(CT || (D == kMaxDenseDim && CPT == 1), "dense widths: 1 .. 8 and 16");
+    __shared__ double s_row[2 * D + 1];
+    __shared__ double s_v[kWaves];
+    __shared__ int64_t s_i[kWaves];
+    __shared__ int s_slot;
+    __shared__ double s_L[CT ? 1 : kMaxDenseDim * kMaxDenseDim];
+    const int d = CT ? D : a.d;
+    const double* Lp = a.linv;
+    if constexpr (!CT) {   // visible after the head's barriers
+        stage_dense_linv(a.linv, d, s_L);
+        Lp = s_L;
+    }
+    const int64_t gw = pick_winner<CT, CT ? D : 1>(a.recs_in, a.nrecs_in, a.rec_stride, d, s_row, s_v, s_i,
+                                                    &s_slot);
+    if (blockIdx.x == 0 && threadIdx.x == 0 && a.idx_out) a.idx_out[a.t - 1] = (uint32_t)gw;
+    double xj[D], gj[D];
+#pragma unroll
+    for (int k = 0; k < D; ++k) {
+        xj[k] = k < d ? s_row[k] : 0.0;
+        gj[k] = k < d ? s_row[d + k] : 0.0;
+    }
+    const double wj = GF ? s_row[2 * d] : 1.0;
+    const double tr = a.tr;
+    double best_v = INFINITY;
+    int64_t best_i = INT64_MAX;
+    const int64_t nunits = (a.n + CPT - 1) / CPT;
+    for (int64_t u = (int64_t)blockIdx.x * kBlock + threadIdx.x; u < nunits; u += (int64_t)gridDim.x * kBlock) {
+        const int64_t i0 = u * CPT;
+        double out[CPT];
+        if constexpr (CT) {
+            Tile<D, GF, false, CPT> t;
+            load_tile<D, GF, false, CPT>(a, i0, t);
+#pragma unroll
+            for (int c = 0; c < CPT; ++c) {
+                double xi[D], gi[D];
+#pragma unroll
+                for (int k = 0; k < D; ++k) { xi[k] = t.x[k][c]; gi[k] = t.g[k][c]; }
+                double kv = pair_dense<D, true>(xi, gi, xj, gj, Lp, D, tr);
+                if constexpr (GF) kv = (kv * t.w[c]) * wj;
+                out[c] = t.a[c] + 2.0 * kv;
+            }
+        } else {
+            double xi[D], gi[D];
+            load_row_padded<D>(a.x + i0, a.ld, d, xi);
+            load_row_padded<D>(a.g + i0, a.ld, d, gi);
+            double kv = pair_dense<D, false>(xi, gi, xj, gj, Lp, d, tr);
+            if constexpr (GF) kv = (kv * a.w[i0]) * wj;
+            out[0] = a.A[i0] + 2.0 * kv;
+        }
+        if constexpr (CPT == 1) {
+            a.A[i0] = out[0];
+        } else {
+#pragma unroll
+            for (int c = 0; c < CPT; c += 2)
+                *reinterpret_cast<double2*>(a.A + i0 + c) = make_double2(out[c], out[c + 1]);
+        }
+#pragma unroll
+        for (int c = 0; c < CPT; ++c)
+            if (i0 + c < a.n && better(out[c], i0 + c, best_v, best_i)) { best_v = out[c]; best_i = i0 + c; }
+    }
+    write_block_record(a, best_v, best_i, s_v, s_i);
+}
+
 // R > 1 ranks: reduce this rank's K block records to ONE rank record (the all-gather payload).
 __global__ __launch_bounds__(kBlock) void greedy_publish(const double* __restrict__ recs, int K,
                                                         int64_t stride, int d,
@@ -560,6 +634,41 @@ hipError_t launch_greedy_step(const GreedyArgs& a, bool diag, int blocks, hipStr
     } else {
         if (ntl) greedy_step_rt<false, false, true><<<blocks, kBlock, 0, s>>>(a);
         else greedy_step_rt<false, false, false><<<blocks, kBlock, 0, s>>>(a);
+    }
+    return hipGetLastError();
+}
+
+// dense preconditioner: two candidates per lane for d <= 8, one for the padded width; the grid caps of
+// the isotropic step kernels (st_tune keys 0 and 6)
+constexpr int kDenseCpt = 2;
+
+int greedy_dense_blocks(int64_t n, int d) {
+    const int64_t per_block = (int64_t)(d <= kMaxCtDim ? kDenseCpt : 1) * kBlock;
+    int64_t b = (n + per_block - 1) / per_block;
+    const int cap = d > kMaxCtDim ? g_rt_max_blocks : g_max_blocks;
+    if (b > cap) b = cap;
+    if (b < 1) b = 1;
+    return (int)b;
+}
+
+template <int D, int CPT>
+static void launch_dense(const GreedyArgs& a, int blocks, hipStream_t s) {
+    if (a.w) greedy_step_dense<D, true, CPT><<<blocks, kBlock, 0, s>>>(a);
+    else greedy_step_dense<D, false, CPT><<<blocks, kBlock, 0, s>>>(a);
+}
+
+hipError_t launch_greedy_step_dense(const GreedyArgs& a, int blocks, hipStream_t s) {
+    if (!a.linv || a.d < 1 || a.d > kMaxDenseDim) return hipErrorInvalidValue;
+    switch (a.d) {
+        case 1: launch_dense<1, kDenseCpt>(a, blocks, s); break;
+        case 2: launch_dense<2, kDenseCpt>(a, blocks, s); break;
+        case 3: launch_dense<3, kDenseCpt>(a, blocks, s); break;
+        case 4: launch_dense<4, kDenseCpt>(a, blocks, s); break;
+        case 5: launch_dense<5, kDenseCpt>(a, blocks, s); break;
+        case 6: launch_dense<6, kDenseCpt>(a, blocks, s); break;
+        case 7: launch_dense<7, kDenseCpt>(a, blocks, s); break;
+        case 8: launch_dense<8, kDenseCpt>(a, blocks, s); break;
+        default: launch_dense<kMaxDenseDim, 1>(a, blocks, s); break;
     }
     return hipGetLastError();
 }

@@ -13,6 +13,7 @@
 
 #include "stein_math.hpp"
 #include "stein_internal.hpp"
+#include "stein_dense.hpp"
 
 namespace st {
 
@@ -108,6 +109,7 @@ struct ColsumArgs {
     int64_t a0, a1;
     double* csum;
     int compact;
+    const double* linv;   // dense Gamma^-1 (stein_dense.hpp), or nullptr
 };
 
 template <int D, bool GF>
@@ -249,6 +251,154 @@ __global__ __launch_bounds__(kColBlock) void ksd_colsum_rt_kernel(ColsumArgs p, 
         }
     }
     if (live) p.csum[i] = acc;
+}
+
+// ------------------------------------------------------------------------------------------
+// Dense preconditioner (PairArgs::linv, d <= kMaxDenseDim): the same three kernels with the pair
+// value of stein_dense.hpp -- D = d for d <= 8, the padded width 16 above (rows zero-padded in
+// registers, L zero-padded in LDS).  k(i, i) needs no special case: dx = 0 makes qs = t1s = t2s = 0 and
+// finish_pair returns the bits of diag_value_ct / diag_value_rt.
+// ------------------------------------------------------------------------------------------
+template <int D>
+__global__ __launch_bounds__(256) void pairs_dense_kernel(PairArgs p, const int64_t* __restrict__ i1,
+                                                          const int64_t* __restrict__ i2, int64_t L,
+                                                          double* __restrict__ out) {
+    constexpr bool CT = D <= kMaxCtDim;
+    __shared__ double s_L[CT ? 1 : kMaxDenseDim * kMaxDenseDim];
+    const int d = CT ? D : p.d;
+    const double* Lp = p.linv;
+    if constexpr (!CT) {
+        stage_dense_linv(p.linv, d, s_L);
+        __syncthreads();
+        Lp = s_L;
+    }
+    for (int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; q < L;
+         q += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t a = i1[q], b = i2[q];
+        double xa[D], ga[D], xb[D], gb[D];
+        load_row_padded<D>(p.x + a, p.ld, d, xa);
+        load_row_padded<D>(p.g + a, p.ld, d, ga);
+        load_row_padded<D>(p.x + b, p.ld, d, xb);
+        load_row_padded<D>(p.g + b, p.ld, d, gb);
+        double kv = pair_dense<D, CT>(xa, ga, xb, gb, Lp, d, p.tr);
+        if (p.w) kv = (kv * p.w[a]) * p.w[b];
+        out[q] = kv;
+    }
+}
+
+template <int D>
+__global__ __launch_bounds__(256) void kmat_dense_kernel(PairArgs p, int64_t k, double* __restrict__ out) {
+    constexpr bool CT = D <= kMaxCtDim;
+    const int64_t bi = blockIdx.y, bj = blockIdx.x;
+    __shared__ double s[2 * D + 1][kChunk];
+    __shared__ double s_L[CT ? 1 : kMaxDenseDim * kMaxDenseDim];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int64_t r = bi * kTile + lane;
+    const int d = CT ? D : p.d;
+    const double* Lp = p.linv;
+    if constexpr (!CT) {   // visible after the first barrier below
+        stage_dense_linv(p.linv, d, s_L);
+        Lp = s_L;
+    }
+    const int64_t rc = r < k ? r : 0;
+    double xr[D], gr[D];
+    load_row_padded<D>(p.x + rc, p.ld, d, xr);
+    load_row_padded<D>(p.g + rc, p.ld, d, gr);
+    const double wr = (p.w && r < k) ? p.w[r] : 1.0;
+    const int64_t cend = (bj * kTile + kTile < k) ? bj * kTile + kTile : k;
+    for (int64_t c0 = bj * kTile; c0 < cend; c0 += kChunk) {
+        __syncthreads();
+        stage_chunk(p, k, c0, s);
+        __syncthreads();
+        if (r < k) {
+            for (int c = wave; c < kChunk; c += 4) {
+                const int64_t cc = c0 + c;
+                if (cc >= k) continue;
+                double xc[D], gc[D];
+#pragma unroll
+                for (int q = 0; q < D; ++q) {
+                    xc[q] = q < d ? s[q][c] : 0.0;
+                    gc[q] = q < d ? s[d + q][c] : 0.0;
+                }
+                double kv = pair_dense<D, CT>(xr, gr, xc, gc, Lp, d, p.tr);
+                if (p.w) {
+                    const double wc = s[2 * d][c];
+                    kv = (r <= cc) ? (kv * wr) * wc : (kv * wc) * wr;
+                }
+                out[cc * k + r] = kv;
+            }
+        }
+    }
+}
+
+// column sums as ksd_colsum_kernel: one thread per column i, rows staged R at a time, a sequential
+// sum per column in increasing a
+template <int D, bool GF>
+__global__ __launch_bounds__(kColBlock) void ksd_colsum_dense_kernel(ColsumArgs p, int d_rt) {
+    constexpr bool CT = D <= kMaxCtDim;
+    constexpr int R = CT ? kColBlock : 64;
+    __shared__ double sx[D][R];
+    __shared__ double sg[D][R];
+    __shared__ double sw[GF ? R : 1];
+    __shared__ double s_L[CT ? 1 : kMaxDenseDim * kMaxDenseDim];
+    const int tid = threadIdx.x;
+    const int d = CT ? D : d_rt;
+    const double* Lp = p.linv;
+    if constexpr (!CT) {   // visible after the first barrier of the row loop
+        stage_dense_linv(p.linv, d, s_L);
+        Lp = s_L;
+    }
+    const int64_t nb = (p.n + kColBlock - 1) / kColBlock;
+    const int64_t c0 = (nb - 1 - (int64_t)blockIdx.x) * kColBlock;
+    const int64_t i = c0 + tid;
+    const int64_t ld = p.ld;
+    const bool live = i < p.n;
+    const int64_t ic = live ? i : 0;
+    double xi[D], gi[D];
+    load_row_padded<D>(p.x + ic, ld, d, xi);
+    load_row_padded<D>(p.g + ic, ld, d, gi);
+    const double wi = (GF && live) ? p.w[i] : 1.0;
+    const double tr = p.tr;
+    const int64_t a_stop = p.a1 < c0 + kColBlock ? p.a1 : c0 + kColBlock;   // rows a < i <= c0 + kColBlock - 1
+    double acc = 0.0;
+    for (int64_t ac = p.a0; ac < a_stop; ac += R) {
+        const int cnt = (int)((a_stop - ac) < R ? (a_stop - ac) : R);
+        __syncthreads();
+        if (tid < cnt) {
+#pragma unroll
+            for (int k = 0; k < D; ++k) {
+                sx[k][tid] = k < d ? p.x[k * ld + ac + tid] : 0.0;
+                sg[k][tid] = k < d ? p.g[k * ld + ac + tid] : 0.0;
+            }
+            if constexpr (GF) sw[tid] = p.w[ac + tid];
+        }
+        __syncthreads();
+        for (int e = 0; e < cnt; ++e) {
+            double xa[D], ga[D];
+#pragma unroll
+            for (int k = 0; k < D; ++k) { xa[k] = sx[k][e]; ga[k] = sg[k][e]; }
+            double kv = pair_dense<D, CT>(xi, gi, xa, ga, Lp, d, tr);
+            if constexpr (GF) kv = (kv * wi) * sw[e];
+            acc = (ac + e < i) ? acc + kv : acc;
+        }
+    }
+    if (live) p.csum[i] = acc;
+}
+
+// call f(std::integral_constant<int, D>) for the dense width of a d-dimensional problem
+template <typename F>
+static void dense_dispatch(int d, F&& f) {
+    switch (d) {
+        case 1: f(std::integral_constant<int, 1>{}); break;
+        case 2: f(std::integral_constant<int, 2>{}); break;
+        case 3: f(std::integral_constant<int, 3>{}); break;
+        case 4: f(std::integral_constant<int, 4>{}); break;
+        case 5: f(std::integral_constant<int, 5>{}); break;
+        case 6: f(std::integral_constant<int, 6>{}); break;
+        case 7: f(std::integral_constant<int, 7>{}); break;
+        case 8: f(std::integral_constant<int, 8>{}); break;
+        default: f(std::integral_constant<int, kMaxDenseDim>{}); break;
+    }
 }
 
 // ks_i = sqrt(S_i) / (i+1), S_i = sum_{a <= i} (2 csum_a + k(a, a)); single block: contiguous
@@ -549,7 +699,8 @@ static void launch_colsum_ct(const ColsumArgs& a, unsigned grid, hipStream_t s) 
 
 hipError_t launch_ksd_colsum(const PairArgs& p, int64_t n, int64_t a0, int64_t a1, double* csum,
                              hipStream_t s) {
-    ColsumArgs a{p.x, p.g, p.w, n, p.ld, p.l, p.tr, a0, a1, csum, arith_compact()};
+    if (p.linv && (p.d < 1 || p.d > kMaxDenseDim)) return hipErrorInvalidValue;
+    ColsumArgs a{p.x, p.g, p.w, n, p.ld, p.l, p.tr, a0, a1, csum, p.linv ? 0 : arith_compact(), p.linv};
     // columns at or below a0 get no rows: zero them, then launch only the blocks above a0
     const int64_t first_block = (a0 + 1) / kColBlock;          // block containing column a0 + 1
     const int64_t nb = (n + kColBlock - 1) / kColBlock;
@@ -562,6 +713,14 @@ hipError_t launch_ksd_colsum(const PairArgs& p, int64_t n, int64_t a0, int64_t a
         return hipSuccess;
     }
     const unsigned grid = (unsigned)(nb - first_block);   // block b -> column block nb-1-b
+    if (p.linv) {
+        dense_dispatch(p.d, [&](auto dt) {
+            constexpr int D = decltype(dt)::value;
+            if (a.w) ksd_colsum_dense_kernel<D, true><<<grid, kColBlock, 0, s>>>(a, p.d);
+            else ksd_colsum_dense_kernel<D, false><<<grid, kColBlock, 0, s>>>(a, p.d);
+        });
+        return hipGetLastError();
+    }
     switch (p.d) {
         case 1: launch_colsum_ct<1>(a, grid, s); break;
         case 2: launch_colsum_ct<2>(a, grid, s); break;
@@ -621,6 +780,13 @@ static int grid_for(int64_t work, int block) {
 
 hipError_t launch_pairs(const PairArgs& p, const int64_t* i1, const int64_t* i2, int64_t L,
                         double* out, hipStream_t s) {
+    if (p.linv) {
+        if (p.d < 1 || p.d > kMaxDenseDim) return hipErrorInvalidValue;
+        dense_dispatch(p.d, [&](auto dt) {
+            pairs_dense_kernel<decltype(dt)::value><<<grid_for(L, 256), 256, 0, s>>>(p, i1, i2, L, out);
+        });
+        return hipGetLastError();
+    }
     pairs_kernel<<<grid_for(L, 256), 256, 0, s>>>(p, i1, i2, L, out);
     return hipGetLastError();
 }
@@ -630,6 +796,11 @@ hipError_t launch_kmat(const PairArgs& p, const int64_t* idx, int64_t k, double*
     (void)idx;
     const int64_t nt = (k + kTile - 1) / kTile;
     dim3 grid((unsigned)nt, (unsigned)nt);
+    if (p.linv) {
+        if (p.d < 1 || p.d > kMaxDenseDim) return hipErrorInvalidValue;
+        dense_dispatch(p.d, [&](auto dt) { kmat_dense_kernel<decltype(dt)::value><<<grid, 256, 0, s>>>(p, k, out); });
+        return hipGetLastError();
+    }
     kmat_kernel<<<grid, 256, 0, s>>>(p, k, out);
     return hipGetLastError();
 }

@@ -7,6 +7,7 @@ namespace st {
 
 constexpr int kMaxDim = 128;     // NumPy pairwise_sum modelled without recursion up to 128 lanes
 constexpr int kMaxCtDim = 8;     // compile-time-d kernels for d <= 8
+constexpr int kMaxDenseDim = 16; // dense preconditioners: d <= 16 (a 32-wide pair needs 256 VGPRs: one wave per SIMD)
 constexpr int kMaxBlocks = 1024; // greedy step grid cap (4 x 256-thread blocks per CU)
 constexpr int kCandHeader = 2;   // candidate record: {val, gidx(bits)} then x[d], g[d], w
 constexpr int64_t kWsControlBytes = 8 * 128 + 128;   // persistent kernel: arrival counters + status
@@ -67,6 +68,7 @@ struct GreedyArgs {
     uint32_t* idx_out;    // device index array; launch t writes idx[t-1]
     int64_t t;            // step being computed (0 = diagonal)
     int compact;          // 1: the compact arithmetic for pairs in range (d <= 8; stein_math.hpp)
+    const double* linv;   // dense Gamma^-1: (d, d) row-major device array (stein_dense.hpp); nullptr: l * I
 };
 
 int greedy_blocks(int64_t n, int d);
@@ -102,6 +104,10 @@ hipError_t launch_greedy_persistent_batch(int count, const BatchProblem* problem
 hipError_t launch_mailbox_handshake(const MailboxPeers& peers, uint64_t* inbox, int rank,
                                     int nranks, uint64_t token, int* ok, hipStream_t s);
 hipError_t launch_greedy_step(const GreedyArgs& a, bool diag, int blocks, hipStream_t s);
+// dense preconditioner (a.linv set, d <= kMaxDenseDim): grid of a run, and one step t >= 1 (step 0 is
+// launch_greedy_step's diagonal with the same grid)
+int greedy_dense_blocks(int64_t n, int d);
+hipError_t launch_greedy_step_dense(const GreedyArgs& a, int blocks, hipStream_t s);
 hipError_t launch_greedy_publish(const double* recs, int K, int64_t stride, int d, double* out,
                                  hipStream_t s);
 hipError_t launch_greedy_finalize(const double* recs, int K, int64_t stride, uint32_t* idx_out,
@@ -164,6 +170,7 @@ struct PairArgs {
     int d;
     double l;
     double tr;
+    const double* linv;   // dense Gamma^-1 (d, d) row-major, d <= kMaxDenseDim; nullptr: l * I
 };
 
 hipError_t launch_pairs(const PairArgs& p, const int64_t* i1, const int64_t* i2, int64_t L,

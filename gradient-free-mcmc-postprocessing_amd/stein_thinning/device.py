@@ -44,7 +44,7 @@ class DedupView:
             nat.ptr(ws), count, ld, nat.ptr(x), nat.ptr(g), nat.ptr(w), nat.ptr(self.rows),
             nat.stream_handle()), 'st_run_compact')
         self.starts = starts                                   # (n,) uint8: row starts a run
-        self.problem = DeviceProblem.from_soa(x, g, w, count, parent.l, parent.tr)
+        self.problem = DeviceProblem.from_soa(x, g, w, count, parent.l, parent.tr, linv=parent.linv)
 
     @property
     def n_unique(self) -> int:
@@ -90,8 +90,44 @@ def pdist_median(sub: np.ndarray, device=None) -> np.float64:
     return np.mean(mid)
 
 
+# widest dense preconditioner the HIP kernels take (csrc/stein_internal.hpp kMaxDenseDim)
+MAX_DENSE_DIM = 16
+
+
+def dense_preconditioner(linv, d: Optional[int] = None):
+    """(L, trace) for a preconditioner that is not l * I (isotropic_scale is None): the C-contiguous
+    float64 matrix the dense kernels read and np.trace(L) exactly as the reference evaluates it.
+    Raises ValueError unless L is (d, d), symmetric (np.allclose(L, L.T)) and positive definite
+    (Cholesky of its symmetric part); NotImplementedError for d > MAX_DENSE_DIM.  The kernels
+    assume symmetry (csrc/stein_dense.hpp): they evaluate dx' L^2 dx as |L dx|^2."""
+    L = np.array(linv, dtype=np.float64, order='C')
+    if L.ndim != 2 or L.shape[0] != L.shape[1] or (d is not None and L.shape[0] != d):
+        raise ValueError(f'preconditioner must be a (d, d) matrix{"" if d is None else f" with d = {d}"}, '
+                         f'got shape {L.shape}')
+    if not np.all(np.isfinite(L)) or not np.allclose(L, L.T):
+        raise ValueError('preconditioner is not a symmetric matrix')
+    try:
+        np.linalg.cholesky((L + L.T) / 2)
+    except np.linalg.LinAlgError:
+        raise ValueError('preconditioner is not positive definite') from None
+    if L.shape[0] > MAX_DENSE_DIM:
+        raise NotImplementedError(f'dense preconditioners run on the HIP engine for d <= {MAX_DENSE_DIM} '
+                                  f'(got d = {L.shape[0]})')
+    return L, float(np.trace(L))
+
+
+def _dense_tensor(linv, device):
+    """The (d, d) device tensor of a dense preconditioner given as a host array or a tensor; None stays None."""
+    import torch
+    if linv is None:
+        return None
+    if isinstance(linv, torch.Tensor):
+        return linv.to(device=device, dtype=torch.float64).contiguous()
+    return torch.from_numpy(np.array(linv, dtype=np.float64, order='C')).to(device)
+
+
 def isotropic_scale(linv: np.ndarray):
-    """(l, trace) if linv == l * I exactly, else None (dense preconditioners: not on the HIP path)."""
+    """(l, trace) if linv == l * I exactly, else None (a dense preconditioner: dense_preconditioner)."""
     linv = np.asarray(linv, dtype=np.float64)
     d = linv.shape[0]
     diag = np.diag(linv)
@@ -106,7 +142,9 @@ class DeviceProblem:
     """Standardised (n, d) sample + score resident on the GPU in SoA layout."""
 
     def __init__(self, sample: np.ndarray, gradient: np.ndarray, weights: Optional[np.ndarray],
-                 linv_scale: float, linv_trace: float, device=None):
+                 linv_scale: float, linv_trace: float, device=None, linv=None):
+        """``linv``: a dense (d, d) preconditioner (host array or device tensor; dense_preconditioner's
+        matrix) -- the dense kernels then run and ``linv_scale`` is unused; None: linv_scale * I."""
         import torch
         self.device = device if device is not None else nat.require_device()
         sample = np.ascontiguousarray(sample, dtype=np.float64)
@@ -117,6 +155,7 @@ class DeviceProblem:
         self.ld = padded_ld(self.n)
         self.l = float(linv_scale)
         self.tr = float(linv_trace)
+        self.linv = _dense_tensor(linv, self.device)
         self.x = self._soa(torch, sample)
         self.g = self._soa(torch, gradient)
         self.w = None
@@ -154,7 +193,7 @@ class DeviceProblem:
 
     @classmethod
     def from_raw_device(cls, x_raw, g_raw, weights: Optional[np.ndarray], scl: np.ndarray,
-                        linv_scale: float, linv_trace: float) -> 'DeviceProblem':
+                        linv_scale: float, linv_trace: float, linv=None) -> 'DeviceProblem':
         """Problem from RAW row-major (n, d) device arrays (thinning._upload_standardized), laid out
         to SoA with the standardisation applied on the device: x / scl, g * scl (st_layout_soa_scaled).
         Everything is queued on the current stream without a host wait (small inputs go up from
@@ -165,6 +204,7 @@ class DeviceProblem:
         self.n, self.d = x_raw.shape
         self.ld = padded_ld(self.n)
         self.l, self.tr = float(linv_scale), float(linv_trace)
+        self.linv = _dense_tensor(linv, self.device)
 
         def up(a):
             return torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64)).pin_memory().to(
@@ -187,15 +227,21 @@ class DeviceProblem:
         return self
 
     @classmethod
-    def from_soa(cls, x_soa, g_soa, w, n: int, linv_scale: float, linv_trace: float):
+    def from_soa(cls, x_soa, g_soa, w, n: int, linv_scale: float, linv_trace: float, linv=None):
         """Wrap already-resident SoA tensors (d, ld) without copies (bench / sharded paths)."""
         self = cls.__new__(cls)
         self.device = x_soa.device
         self.d, self.ld = x_soa.shape
         self.n = int(n)
         self.l, self.tr = float(linv_scale), float(linv_trace)
+        self.linv = _dense_tensor(linv, self.device)
         self.x, self.g, self.w = x_soa, g_soa, w
         return self
+
+    def set_preconditioner(self, linv_scale: float, linv_trace: float, linv=None) -> None:
+        """Fill in the preconditioner of a problem uploaded before it was known (thinning._attach)."""
+        self.l, self.tr = float(linv_scale), float(linv_trace)
+        self.linv = _dense_tensor(linv, self.device)
 
     # -- greedy ------------------------------------------------------------------------------
     def greedy_buffers(self, n_points: int):
@@ -207,7 +253,10 @@ class DeviceProblem:
         return idx, a, ws
 
     def greedy_launch(self, n_points: int, idx, a, ws) -> None:
-        """Enqueue the whole greedy run on the current stream (no sync)."""
+        """Enqueue the whole greedy run on the current stream (no sync); a dense preconditioner runs
+        st_greedy_dense (always one launch per step)."""
+        if self.linv is not None:
+            return self._greedy_dense_launch(n_points, idx, a, ws)
         nat.check(nat.lib().st_greedy(
             nat.ptr(self.x), nat.ptr(self.g), nat.ptr(self.w), self.n, self.d, self.ld,
             self.l, self.tr, int(n_points), nat.ptr(idx), nat.ptr(a), nat.ptr(ws),
@@ -216,10 +265,18 @@ class DeviceProblem:
     def greedy_steps_launch(self, n_points: int, idx, a, ws) -> None:
         """Enqueue the whole greedy run on the launch-per-step kernels (st_greedy_steps: no
         co-residency requirement, the same bits as the persistent kernel)."""
+        if self.linv is not None:
+            return self._greedy_dense_launch(n_points, idx, a, ws)
         nat.check(nat.lib().st_greedy_steps(
             nat.ptr(self.x), nat.ptr(self.g), nat.ptr(self.w), self.n, self.d, self.ld,
             self.l, self.tr, 0, int(n_points), int(n_points), nat.ptr(idx), nat.ptr(a), nat.ptr(ws),
             ws.numel() * 8, nat.stream_handle()), 'st_greedy_steps')
+
+    def _greedy_dense_launch(self, n_points: int, idx, a, ws) -> None:
+        nat.check(nat.lib().st_greedy_dense(
+            nat.ptr(self.x), nat.ptr(self.g), nat.ptr(self.w), self.n, self.d, self.ld,
+            nat.ptr(self.linv), self.tr, int(n_points), nat.ptr(idx), nat.ptr(a), nat.ptr(ws),
+            ws.numel() * 8, nat.stream_handle()), 'st_greedy_dense')
 
     def guard_mode(self, guard: bool = True) -> Optional[str]:
         """How ``greedy(guard=True)`` -- the drop-in thin's call -- keeps the reference's selection under
@@ -229,6 +286,8 @@ class DeviceProblem:
         step whose argmin rests on sums closer than the arithmetic's error band (st_greedy_near_tie) and
         a flagged thin is re-run with the exact arithmetic; 'exact' for the other d <= 8, whose
         launch-per-step kernels carry no flag: the thin runs with the exact arithmetic."""
+        if self.linv is not None:   # one dense arithmetic: nothing to guard
+            return None
         if not guard or not nat.near_tie_guard() or self.d > 8 or nat.arithmetic() != 'compact':
             return None
         return 'kernel' if self.d in (2, 4) else 'exact'
@@ -338,9 +397,12 @@ class DeviceProblem:
         (>= 4 x DEDUP_MIN_SAVING_S)?  After: do the dropped rows save >= DEDUP_MIN_SAVING_S?  Per-pair
         costs measured on MI355X: ~1.8 ps per Langevin d = 4 pair on the
         persistent kernel above its per-step exchange floor, scaled by the flop count for d <= 8;
-        the launch-per-step kernels of d > 8 stream (16 d + 24) B per pair at ~5 TB/s."""
+        the launch-per-step kernels of d > 8 stream (16 d + 24) B per pair at ~5 TB/s; a dense
+        preconditioner adds its d^2 + 3 d fma per pair to the flop count (an estimate, not measured)."""
         d = self.d
-        if d <= 8:
+        if self.linv is not None:
+            per_pair = 1.8e-12 * (2 * d * d + 8 * d + 40 + (2 if self.w is not None else 0)) / 88.0
+        elif d <= 8:
             per_pair = 1.8e-12 * (12 * d + 40 + (2 if self.w is not None else 0)) / 88.0
         else:
             per_pair = (16 * d + 24) / 5e12
@@ -363,7 +425,11 @@ class DeviceProblem:
         import torch
         L = int(t1.shape[0])
         out = torch.empty(L, dtype=torch.float64, device=self.device)
-        if L:
+        if L and self.linv is not None:
+            nat.check(nat.lib().st_kernel_pairs_dense(
+                nat.ptr(self.x), nat.ptr(self.g), nat.ptr(self.w), self.ld, self.d, nat.ptr(self.linv), self.tr,
+                nat.ptr(t1), nat.ptr(t2), L, nat.ptr(out), nat.stream_handle()), 'st_kernel_pairs_dense')
+        elif L:
             nat.check(nat.lib().st_kernel_pairs(
                 nat.ptr(self.x), nat.ptr(self.g), nat.ptr(self.w), self.ld, self.d, self.l, self.tr,
                 nat.ptr(t1), nat.ptr(t2), L, nat.ptr(out), nat.stream_handle()), 'st_kernel_pairs')
@@ -386,7 +452,7 @@ class DeviceProblem:
         if self.w is not None:
             w = torch.zeros(ld, dtype=torch.float64, device=self.device)
             w[:m] = self.w.index_select(0, ti)
-        return DeviceProblem.from_soa(x, g, w, m, self.l, self.tr)
+        return DeviceProblem.from_soa(x, g, w, m, self.l, self.tr, linv=self.linv)
 
     def ksd(self, m: int) -> np.ndarray:
         """Cumulative KSD over rows 0..m-1 of this problem."""
@@ -396,6 +462,11 @@ class DeviceProblem:
         ws_bytes = int(nat.lib().st_ksd_workspace_bytes(m, self.ld))
         ws = torch.empty((ws_bytes + 7) // 8, dtype=torch.float64, device=self.device)
         ks = torch.empty(m, dtype=torch.float64, device=self.device)
+        if self.linv is not None:
+            nat.check(nat.lib().st_ksd_cumulative_dense(
+                nat.ptr(self.x), nat.ptr(self.g), nat.ptr(self.w), m, self.ld, self.d, nat.ptr(self.linv), self.tr,
+                nat.ptr(ks), nat.ptr(ws), ws.numel() * 8, nat.stream_handle()), 'st_ksd_cumulative_dense')
+            return ks.cpu().numpy()
         nat.check(nat.lib().st_ksd_cumulative(
             nat.ptr(self.x), nat.ptr(self.g), nat.ptr(self.w), m, self.ld, self.d, self.l, self.tr,
             nat.ptr(ks), nat.ptr(ws), ws.numel() * 8, nat.stream_handle()), 'st_ksd_cumulative')
@@ -406,6 +477,11 @@ class DeviceProblem:
         if k == 0:
             return np.zeros((0, 0))
         out = torch.empty((k, k), dtype=torch.float64, device=self.device)
+        if self.linv is not None:
+            nat.check(nat.lib().st_kmat_dense(
+                nat.ptr(self.x), nat.ptr(self.g), nat.ptr(self.w), k, self.ld, self.d, nat.ptr(self.linv), self.tr,
+                nat.ptr(out), nat.stream_handle()), 'st_kmat_dense')
+            return out.cpu().numpy()
         nat.check(nat.lib().st_kmat(
             nat.ptr(self.x), nat.ptr(self.g), nat.ptr(self.w), k, self.ld, self.d, self.l, self.tr,
             nat.ptr(out), nat.stream_handle()), 'st_kmat')
@@ -455,7 +531,7 @@ def greedy_concurrent(problems, n_points: int, in_flight: Optional[int] = None, 
     other.  First, groups of up to ``batch`` (default BATCH) problems of one d go to the device as
     ONE launch each (st_greedy_batch); a group of 4 or more that the batch kernel declines (its
     problems plan onto different kernels) is split into its smaller and larger half, each tried
-    again; what is left uses the streams.
+    again; what is left -- and every problem with a dense preconditioner -- uses the streams.
     Every result equals
     ``problem.greedy(n_points, dedup=dedup, guard=guard)``; a launch whose bounded waits expired anyway (another
     process's kernels held CUs) is re-run alone.  Returns one uint32 index array per problem."""
@@ -497,7 +573,7 @@ def greedy_concurrent(problems, n_points: int, in_flight: Optional[int] = None, 
     if kb > 1:   # batch launches over groups of one d (and weights or none), in order; the batch kernel
         groups = {}   # runs the compact arithmetic, so the problems the guard runs exactly go to the streams
         for i, p in enumerate(runs):
-            if modes[i] != 'exact':
+            if modes[i] != 'exact' and p.linv is None:   # dense problems take the streams (no batch kernel)
                 groups.setdefault((p.d, p.w is not None), []).append(i)
         for ids in groups.values():
             for j in range(0, len(ids), kb):

@@ -67,6 +67,9 @@ def pair_scale(torch, xi, gi, xj, gj, l: float, tr: float):
 def greedy_margins(prob, n_points: int) -> GreedyMargins:
     """Greedy run on ``prob`` (a DeviceProblem) with the margin bookkeeping above, one step launch
     at a time on the current stream (a diagnostic: a few small device reductions per step)."""
+    if getattr(prob, 'linv', None) is not None:
+        raise NotImplementedError('greedy_margins: the error band is modelled for the isotropic arithmetics only, '
+                                  'not for a dense preconditioner')
     import torch
     n, m = prob.n, int(n_points)
     arith = nat.arithmetic() if prob.d <= 8 else 'exact'
@@ -135,6 +138,9 @@ def greedy_margins(prob, n_points: int) -> GreedyMargins:
 
 def thin_margins(sample, gradient, n_points: int, standardize: bool = True, preconditioner='id') -> GreedyMargins:
     """``thin``'s selection with the per-step margin diagnostics (same arguments as thin)."""
+    if isinstance(preconditioner, str) and preconditioner == 'smpcov':
+        raise NotImplementedError("thin_margins: the error band is modelled for the isotropic arithmetics only, "
+                                  "not for the dense preconditioner 'smpcov'")
     from .thinning import _make_stein_integrand
     return greedy_margins(_make_stein_integrand(sample, gradient, standardize, preconditioner).device_problem(),
                           n_points)
@@ -143,6 +149,9 @@ def thin_margins(sample, gradient, n_points: int, standardize: bool = True, prec
 def thin_gf_margins(sample, log_p, log_q, gradient_q, n_points: int, standardize: bool = True,
                     range_cap=None, preconditioner='id') -> GreedyMargins:
     """``thin_gf``'s selection with the per-step margin diagnostics (same arguments as thin_gf)."""
+    if isinstance(preconditioner, str) and preconditioner == 'smpcov':
+        raise NotImplementedError("thin_gf_margins: the error band is modelled for the isotropic arithmetics only, "
+                                  "not for the dense preconditioner 'smpcov'")
     from .thinning import _make_stein_gf_integrand
     integrand = _make_stein_gf_integrand(sample, log_p, log_q, gradient_q, standardize, range_cap, preconditioner)
     return greedy_margins(integrand.device_problem(), n_points)

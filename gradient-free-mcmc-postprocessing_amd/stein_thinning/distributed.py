@@ -545,9 +545,18 @@ def run_ksd_sharded(backend, n: int, group=None) -> np.ndarray:
     return backend.finish(c)
 
 
+def _refuse_dense(what: str, integrand=None, preconditioner=None) -> None:
+    """Dense preconditioners ('smpcov', or an integrand built on a full matrix) run on one device only."""
+    if (isinstance(preconditioner, str) and preconditioner == 'smpcov') or \
+            getattr(integrand, 'linv_dense', None) is not None:
+        raise NotImplementedError(f'{what}: dense preconditioners are not sharded across ranks (the multi-rank '
+                                  f'kernels carry the isotropic scale only); use thin / stein.ksd on one device')
+
+
 def ksd_sharded(integrand: SteinIntegrand, n: int, group=None) -> np.ndarray:
     """Cumulative KSD of rows 0..n-1 of ``integrand`` (stein_thinning.stein.ksd semantics) with
     the O(n^2) pair work split over the ranks of ``group``."""
+    _refuse_dense('ksd_sharded', integrand)
     return run_ksd_sharded(HipKsdBackend(integrand, n), int(n), group)
 
 
@@ -561,12 +570,14 @@ def _world(group):
 def thin_sharded(sample, gradient, n_points: int, standardize: bool = True, preconditioner='id',
                  group=None) -> np.ndarray:
     """``thin`` with the candidate rows sharded over the ranks of ``group`` (identical result)."""
+    _refuse_dense('thin_sharded', preconditioner=preconditioner)
     integrand = _make_stein_integrand(sample, gradient, standardize, preconditioner)
     return _thin_sharded_integrand(integrand, n_points, group)
 
 
 def thin_gf_sharded(sample, log_p, log_q, gradient_q, n_points: int, standardize: bool = True,
                     range_cap: Optional[float] = None, preconditioner='id', group=None) -> np.ndarray:
+    _refuse_dense('thin_gf_sharded', preconditioner=preconditioner)
     integrand = _make_stein_gf_integrand(sample, log_p, log_q, gradient_q, standardize, range_cap,
                                          preconditioner)
     return _thin_sharded_integrand(integrand, n_points, group)
@@ -686,6 +697,7 @@ def thin_across_ranks(integrand: SteinIntegrand, n_points: int, group=None) -> n
     rank must call it with the same problem -- checked first; ranks thinning different samples (the
     reference's per-chain fan-out, ``code/src/utils/parallel.py:48-52``) get a ValueError and should
     leave sharding off."""
+    _refuse_dense('thin_across_ranks', integrand)
     if not _group_same(_problem_digest(integrand, n_points), group):
         raise ValueError('thin() under torch.distributed: the ranks hold different problems; '
                          'leave row sharding off (ST_SHARD_THIN unset / set_rank_sharding(False)) '

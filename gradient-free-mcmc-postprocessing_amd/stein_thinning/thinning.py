@@ -140,7 +140,7 @@ class SteinIntegrand:
 
     def __init__(self, sample: np.ndarray, gradient: np.ndarray, linv: np.ndarray,
                  weights: Optional[np.ndarray] = None):
-        from .device import isotropic_scale
+        from .device import dense_preconditioner, isotropic_scale
         self._sample = sample
         self._gradient = gradient
         self._materialize = None   # deferred host arrays (_deferred): computed on first access
@@ -148,8 +148,14 @@ class SteinIntegrand:
         self.linv = linv
         self.weights = weights
         iso = isotropic_scale(linv)
+        # a dense preconditioner (anything but l * I): validated here -- ValueError unless (d, d), symmetric and
+        # positive definite, NotImplementedError for d > 16 -- and run by the dense kernels; linv_scale is unused
+        self.linv_dense = None
         if iso is None:
-            raise NotImplementedError('only isotropic preconditioners run on the HIP engine')
+            self.linv_dense, tr = dense_preconditioner(linv, sample.shape[1] if sample.shape[1] else None)
+            iso = (0.0, tr)
+        elif not iso[0] > 0:   # l * I with l <= 0 (e.g. -I) is no preconditioner either
+            raise ValueError('preconditioner is not positive definite')
         self.linv_scale, self.linv_trace = iso
         self._problem = None
         self._base: Optional['SteinIntegrand'] = None   # views: the integrand whose rows these index
@@ -233,7 +239,7 @@ class SteinIntegrand:
             else:
                 from .device import DeviceProblem
                 self._problem = DeviceProblem(self.sample, self.gradient, self.weights,
-                                              self.linv_scale, self.linv_trace)
+                                              self.linv_scale, self.linv_trace, linv=self.linv_dense)
                 # a page-locked source is copied asynchronously, and torch records no event for a
                 # buffer it did not allocate: wait here, so the copy has landed whatever happens to the
                 # host arrays or the stream the problem is used on next
@@ -392,7 +398,7 @@ def _device_integrand(up, preconditioner, weights: Optional[np.ndarray]) -> Stei
 
 def _attach(integrand: SteinIntegrand, prob) -> SteinIntegrand:
     if prob is not None:
-        prob.l, prob.tr = float(integrand.linv_scale), float(integrand.linv_trace)
+        prob.set_preconditioner(integrand.linv_scale, integrand.linv_trace, integrand.linv_dense)
         # the preconditioner took longer than the DMA: this normally returns at once, and it keeps
         # the integrand safe to use from any stream afterwards
         prob.wait_upload()
@@ -405,8 +411,15 @@ def _make_stein_integrand(sample, gradient, standardize: bool = True, preconditi
         return _make_stein_integrand_here(sample, gradient, standardize, preconditioner)
 
 
+def _needs_host_sample(preconditioner) -> bool:
+    """'smpcov' reads every standardised row on the host (np.cov), so its inputs take the host route: ROCm
+    tensors come down through _as_numpy and the early device upload is skipped -- slower input preparation
+    than the other preconditioners', accepted for a d x d covariance."""
+    return isinstance(preconditioner, str) and preconditioner == 'smpcov'
+
+
 def _make_stein_integrand_here(sample, gradient, standardize, preconditioner) -> SteinIntegrand:
-    up = _upload_standardized(sample, gradient, standardize)
+    up = None if _needs_host_sample(preconditioner) else _upload_standardized(sample, gradient, standardize)
     if up is not None:
         return _device_integrand(up, preconditioner, None)
     sample, gradient = _validate_and_standardize(sample, gradient, standardize)
@@ -424,7 +437,7 @@ def _make_stein_gf_integrand(sample, log_p, log_q, gradient_q, standardize: bool
 
 def _make_stein_gf_integrand_here(sample, log_p, log_q, gradient_q, standardize, range_cap,
                                   preconditioner) -> SteinIntegrand:
-    up = _upload_standardized(sample, gradient_q, standardize)
+    up = None if _needs_host_sample(preconditioner) else _upload_standardized(sample, gradient_q, standardize)
     if up is None:
         sample, gradient_q = _validate_and_standardize(sample, gradient_q, standardize)
         n = sample.shape[0]
@@ -545,7 +558,9 @@ def _on_home(a):
 
 def thin(sample, gradient, n_points: int, standardize: bool = True, preconditioner='id') -> np.ndarray:
     """Stein thinning: indices of ``n_points`` rows of ``sample`` greedily minimising the KSD.  ``sample`` /
-    ``gradient`` may be NumPy arrays or ROCm tensors (used in place on their device: _download_standardized)."""
+    ``gradient`` may be NumPy arrays or ROCm tensors (used in place on their device: _download_standardized).
+    ``preconditioner``: 'id', 'med', 'sclmed', a number, or 'smpcov' -- the inverse sample covariance, a dense
+    matrix (d <= 16; kernel.make_precon), which reads the whole standardised sample on the host first."""
     with _on_home(sample):
         integrand = _make_stein_integrand(sample, gradient, standardize, preconditioner)
         return _greedy_search(n_points, integrand)

@@ -19,6 +19,9 @@
  *     all device pointers 16-byte aligned;
  *   - the preconditioner is isotropic Gamma^-1 = linv_scale * I ('id', 'med', 'sclmed', float
  *     options of the reference); linv_trace = np.trace(Gamma^-1) computed on the host;
+ *     the *_dense entry points take a dense symmetric positive-definite Gamma^-1 instead ('smpcov',
+ *     the inverse sample covariance): `linv` = (d, d) row-major doubles on the device, d <= 16
+ *     (see "Dense preconditioners" below); symmetry and definiteness are the caller's to check;
  *   - weights == NULL selects the Langevin Stein kernel k_P; weights = w = exp(log q - log p)
  *     (anchored) selects the gradient-free kernel k_PQ(i,j) = w_i w_j k_Q(i,j) (report.tex:390-400);
  *   - return value: ST_OK (0) or a negative ST_ERR_*; st_last_error() describes the last failure
@@ -37,7 +40,7 @@ extern "C" {
 
 #define ST_OK 0
 #define ST_ERR_INVALID (-1)     /* bad argument: sizes, null pointers, alignment */
-#define ST_ERR_UNSUPPORTED (-2) /* e.g. d > 128 */
+#define ST_ERR_UNSUPPORTED (-2) /* e.g. d > 128; a dense preconditioner with d > 16 */
 #define ST_ERR_HIP (-3)         /* HIP runtime error (launch / memset) */
 
 int st_abi_version(void);
@@ -361,6 +364,49 @@ int st_ksd_finish(const double *x_soa, const double *g_soa, const double *weight
 int st_kmat(const double *x_soa, const double *g_soa, const double *weights, int64_t k,
             int64_t ld, int32_t d, double linv_scale, double linv_trace, double *kmat_out,
             void *stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Dense preconditioners -- Gamma^-1 = L, any symmetric positive-definite (d, d) matrix, d <= 16 (the
+ * reference's vfk0_imq takes any linv; upstream's preconditioner='smpcov' is the inverse sample
+ * covariance).  Each function takes the arguments of its isotropic twin with linv_scale replaced by
+ * `linv`: (d, d) row-major doubles on the device, 16-byte aligned; linv_trace = np.trace(L) from the host.
+ * Validation before any HIP call: NULL or misaligned pointers ST_ERR_INVALID, d > 16 ST_ERR_UNSUPPORTED.
+ *
+ * Arithmetic -- one definition for every dense kernel, so a pair's bits do not depend on the entry
+ * point (separately rounded operations except where fma is written).  With dx = x_i - x_j, ds = g_i - g_j:
+ *   for r = 0 .. d-1:  y_r = L[r][0] dx_0, then y_r = fma(L[r][k], dx_k, y_r) for k = 1 .. d-1;
+ *   qs  = y_0 dx_0, then fma(y_r, dx_r, qs);  t1s = y_0 y_0, then fma(y_r, y_r, t1s);
+ *   t2s = y_0 ds_0, then fma(y_r, ds_r, t2s)                                          (r = 1 .. d-1);
+ *   t3s = sum_k g_i,k g_j,k in NumPy's pairwise order, as the isotropic kernels compute it;
+ *   qf = 1 + qs;  k = (-3 t1s / qf^2.5 + (linv_trace + t2s) / qf^1.5) + t3s / sqrt(qf), the powers
+ *   correctly rounded.
+ * This is the reference's formula with two changes that hold for symmetric L only: dx' L^2 dx is
+ * evaluated as |L dx|^2 and (L ds) . dx as (L dx) . ds.  Swapping i and j negates dx, ds and y
+ * exactly, so k(i, j) and k(j, i) are equal bit for bit; k(i, i) = linv_trace + t3s as in the isotropic
+ * kernels.  d = 9 .. 16 run at a padded width of 16 (exact zeros added).  st_tune key 11 and the near-tie
+ * guard do not apply: after st_greedy_dense, st_greedy_near_tie reports -2.
+ *
+ * st_greedy_dense always takes one launch per step (the step kernels' hand-off, no wait inside a
+ * kernel); workspace as st_greedy (st_greedy_workspace_bytes).
+ * st_ksd_cumulative_dense == st_ksd_colsum_dense over [0, m) followed by st_ksd_finish (k(a, a)
+ * depends on linv_trace only).
+ * ---------------------------------------------------------------------------------------- */
+int st_greedy_dense(const double *x_soa, const double *g_soa, const double *weights, int64_t n,
+                    int32_t d, int64_t ld, const double *linv, double linv_trace, int64_t n_points,
+                    uint32_t *idx_out, double *a_work, void *workspace, int64_t workspace_bytes,
+                    void *stream);
+int st_kernel_pairs_dense(const double *x_soa, const double *g_soa, const double *weights, int64_t ld,
+                          int32_t d, const double *linv, double linv_trace, const int64_t *i1,
+                          const int64_t *i2, int64_t n_pairs, double *out, void *stream);
+int st_kmat_dense(const double *x_soa, const double *g_soa, const double *weights, int64_t k,
+                  int64_t ld, int32_t d, const double *linv, double linv_trace, double *kmat_out,
+                  void *stream);
+int st_ksd_colsum_dense(const double *x_soa, const double *g_soa, const double *weights, int64_t n,
+                        int64_t ld, int32_t d, const double *linv, double linv_trace, int64_t row_begin,
+                        int64_t row_end, double *csum_out, void *stream);
+int st_ksd_cumulative_dense(const double *x_soa, const double *g_soa, const double *weights, int64_t m,
+                            int64_t ld, int32_t d, const double *linv, double linv_trace, double *ks_out,
+                            void *workspace, int64_t workspace_bytes, void *stream);
 
 /* ------------------------------------------------------------------------------------------
  * Energy distance -- replaces dcor.energy_distance(x, y) (V-statistic, exponent 1) as used by the
