@@ -156,6 +156,61 @@ def test_host_side_validation_of_the_newer_entry_points(libpath):
     assert lib.st_greedy_batch(*a) == inv and b'problem 1' in lib.st_last_error()
 
 
+def test_host_side_validation_of_the_kde_and_distance_entry_points(libpath):
+    """st_kde_logpdf_grad, the workspace sizes and st_tune keys 13 / 14: every check precedes any HIP call."""
+    import ctypes
+    from stein_thinning import _native
+    lib = _native.load_library(libpath)
+    inv, uns = _native.ST_ERR_INVALID, _native.ST_ERR_UNSUPPORTED
+    buf = (ctypes.c_double * 64)()
+    p = ctypes.cast(buf, ctypes.c_void_p)
+    # p, ldp, n, log_weights, log_weight_uniform, q, ldq, m, d, log_norm, whiten, log_q, grad, ws, ws_bytes, stream
+    base = [p, 64, 10, None, -2.3, p, 64, 7, 4, 0.5, p, p, p, None, 0, None]
+
+    def call(**kw):
+        names = ['p', 'ldp', 'n', 'logw', 'logw0', 'q', 'ldq', 'm', 'd', 'log_norm', 'whiten', 'log_q', 'grad',
+                 'ws', 'ws_bytes', 'stream']
+        a = list(base)
+        for k, v in kw.items():
+            a[names.index(k)] = v
+        return lib.st_kde_logpdf_grad(*a)
+
+    assert call(m=0) == _native.ST_OK
+    assert call(m=0, p=None, q=None, whiten=None, log_q=None, grad=None) == _native.ST_OK
+    for name in ('p', 'q', 'whiten', 'log_q', 'grad'):
+        assert call(**{name: None}) == inv, name
+        assert b'NULL' in lib.st_last_error()
+    assert call(d=0) == uns and call(d=129) == uns
+    assert call(n=0) == inv
+    assert call(ldp=9) == inv and call(ldq=6) == inv
+    assert call(d=9) == inv                                          # NULL workspace
+    assert b'workspace' in lib.st_last_error()
+    assert call(d=9, ws=p, ws_bytes=7 * 9 * 8 - 8) == inv            # short workspace
+    assert call(d=9, ws=None, ws_bytes=7 * 9 * 8) == inv             # the size without the memory
+    for m in (0, 1, 7, 300):
+        assert lib.st_kde_workspace_bytes(m, 8) == 0
+        assert lib.st_kde_workspace_bytes(m, 9) == 72 * m
+    assert lib.st_kde_workspace_bytes(7, 128) == 7 * 128 * 8
+    assert lib.st_kde_workspace_bytes(-1, 4) == -1 and lib.st_kde_workspace_bytes(7, 0) == -1
+    assert lib.st_kde_workspace_bytes(7, 129) == -1
+    # energy-distance workspace: a negative or reversed range
+    assert lib.st_distance_workspace_bytes(10, -1, 5) == -1
+    assert lib.st_distance_workspace_bytes(10, 5, 4) == -1
+    assert lib.st_distance_workspace_bytes(-1, 0, 5) == -1
+    assert lib.st_distance_workspace_bytes(10, 5, 5) == 0
+    assert lib.st_distance_workspace_bytes(300, 0, 3073) == 4 * 300 * 8
+    # kernel variant (key 13) and work units (key 14): write-only keys, restored with -1
+    try:
+        assert lib.st_tune(13, 7) != 0 and lib.st_tune(13, -2) != 0
+        assert lib.st_tune(14, 255) != 0 and lib.st_tune(14, (1 << 22) + 1) != 0 and lib.st_tune(14, 0) != 0
+        assert lib.st_tune(14, 256) == 0
+        assert lib.st_distance_workspace_bytes(4096, 100, 16485) == 16 * 4096 * 8
+        assert lib.st_tune(14, 1 << 22) == 0
+    finally:
+        assert lib.st_tune(13, -1) == 0 and lib.st_tune(14, -1) == 0
+    assert lib.st_tune_get(13) == -2 ** 31 and lib.st_tune_get(14) == -2 ** 31
+
+
 def test_library_is_gfx950_only(libpath):
     # the embedded code-object bundle names its target: amdgcn-amd-amdhsa--gfx950
     blob = open(libpath, 'rb').read()
