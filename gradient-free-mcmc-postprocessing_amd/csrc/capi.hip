@@ -530,6 +530,27 @@ int st_proxy_logpdf_grad(const double* x, int64_t n, int32_t d, const double* lo
     return hip_check(st::launch_proxy(a, static_cast<hipStream_t>(stream)), "proxy launch");
 }
 
+int st_mixture_logpdf_score(const double* x, int64_t n, int32_t d, int32_t k, const double* log_coef,
+                            const double* means, const double* precision, double* log_p_out,
+                            double* score_out, void* stream) {
+    if (n < 0) return fail(ST_ERR_INVALID, "n must be >= 0 (got %lld)", (long long)n);
+    if (d < 1) return fail(ST_ERR_INVALID, "d must be >= 1 (got %d)", d);
+    if (k < 1) return fail(ST_ERR_INVALID, "k must be >= 1 (got %d)", k);
+    if (!log_coef || !means || !precision || (n > 0 && (!x || !log_p_out || !score_out)))
+        return fail(ST_ERR_INVALID, "NULL pointer");
+    const uintptr_t bits = reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(log_coef) |
+                           reinterpret_cast<uintptr_t>(means) | reinterpret_cast<uintptr_t>(precision) |
+                           reinterpret_cast<uintptr_t>(log_p_out) | reinterpret_cast<uintptr_t>(score_out);
+    if (bits & 7u) return fail(ST_ERR_INVALID, "device arrays must be 8-byte aligned");
+    if (d > st::kMixtureMaxDim)
+        return fail(ST_ERR_UNSUPPORTED, "d = %d exceeds the mixture kernels' maximum %d", d, st::kMixtureMaxDim);
+    if (k > st::kMixtureMaxComponents)
+        return fail(ST_ERR_UNSUPPORTED, "k = %d components exceed the maximum %d", k, st::kMixtureMaxComponents);
+    if (n == 0) return ST_OK;
+    st::MixtureArgs a{x, log_coef, means, precision, n, d, k, log_p_out, score_out};
+    return hip_check(st::launch_mixture(a, static_cast<hipStream_t>(stream)), "mixture launch");
+}
+
 // accepted RK45 steps recorded per point by the two-phase gradient (typical: ~32 at the reference's
 // tolerances); a point that takes more is recomputed by the single-phase kernel
 constexpr int kLvStepCap = 64;

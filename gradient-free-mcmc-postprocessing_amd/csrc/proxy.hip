@@ -605,3 +605,5 @@ hipError_t launch_proxy(const ProxyArgs& a, hipStream_t s) {
 }
 
 }  // namespace st
+
+#include "mixture.hpp"   // the Gaussian-mixture kernels: this file's tile constants and matrix-core lane maps

@@ -131,6 +131,20 @@ hipError_t launch_kde(const double* p, int64_t ldp, int64_t n, const double* log
                       double* log_q, double* grad, double* ws, hipStream_t s);
 hipError_t launch_proxy(const ProxyArgs& a, hipStream_t s);
 int proxy_tune(int value);   // st_tune key 7
+constexpr int kMixtureMaxDim = 64;     // the matrix-core kernel's widest instantiation
+constexpr int kMixtureMaxComponents = 1024;
+struct MixtureArgs {
+    const double* x;         // row-major (n, d) raw sample
+    const double* log_coef;  // (k) a_c = log w_c - (d log 2 pi + log det Sigma_c) / 2; -inf: skipped
+    const double* means;     // (k, d) row-major
+    const double* P;         // (k, d, d) row-major, np.linalg.inv(Sigma_c)
+    int64_t n;
+    int d;
+    int k;
+    double* log_p;           // (n)
+    double* score;           // row-major (n, d)
+};
+hipError_t launch_mixture(const MixtureArgs& a, hipStream_t s);   // csrc/mixture.hpp (in proxy.hip)
 int dist_tune(int value);    // st_tune key 13 (energy kernel variant)
 
 struct LvArgs {

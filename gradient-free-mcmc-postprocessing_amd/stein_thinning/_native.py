@@ -115,6 +115,7 @@ SIGNATURES = {
                                                _c_dp, _c_dp, _i64, _c_dp]),
     'st_proxy_logpdf_grad': (ctypes.c_int, [_c_dp, _i64, _i32, _c_dp, _c_dp, _c_dp, _f64, _f64, _c_dp,
                                             _c_dp, _c_dp]),
+    'st_mixture_logpdf_score': (ctypes.c_int, [_c_dp, _i64, _i32, _i32, _c_dp, _c_dp, _c_dp, _c_dp, _c_dp, _c_dp]),
 }
 ABI_VERSION = 1
 

@@ -206,9 +206,21 @@ def gaussian_thin(sample, log_p, mean, cov, thinned_size: int, range_cap: Option
     return thin_gf(sample, log_p, log_q, gradient_q, thinned_size, range_cap=range_cap, preconditioner='med')
 
 
+def mixture_thin(sample, log_p, weights, means, covs, thinned_size: int,
+                 range_cap: Optional[float] = 200) -> np.ndarray:
+    """``gaussian_thin`` with a Gaussian-mixture proxy q = sum_c w_c N(mu_c, Sigma_c) (``mixture_proxy``:
+    st_mixture_logpdf_score) -- the natural proxy of a multimodal target."""
+    from .thinning import thin_gf
+    log_q, gradient_q = mixture_proxy(sample, weights, means, covs)
+    return thin_gf(sample, log_p, log_q, gradient_q, thinned_size, range_cap=range_cap, preconditioner='med')
+
+
 def thin_gf_t(sample, log_p, t_mu, t_scale, t_df, thinned_size: int, range_cap: Optional[float] = 200) -> np.ndarray:
     """Gradient_free_Student_t.ipynb cell 40 with the proxy evaluated on the GPU (that cell keeps
     thin_gf's default preconditioner 'id')."""
     from .thinning import thin_gf
     log_q, gradient_q = student_t_proxy(sample, t_mu, t_scale, t_df)
     return thin_gf(sample, log_p, log_q, gradient_q, thinned_size, range_cap=range_cap)
+
+
+from .mixture import mixture_logpdf_score as mixture_proxy  # noqa: E402  (mixture.py imports _psd from here)

@@ -274,6 +274,28 @@ int st_proxy_logpdf_grad(const double *x, int64_t n, int32_t d, const double *lo
                          double *log_q_out, double *grad_out, void *stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Gaussian mixture -- replaces logpdf / score of make_mvn_mixture (code/src/utils/mvn.py), the
+ * target of Gaussian_mixture.ipynb, and serves as a mixture proxy q for thin_gf.  Per row x and
+ * component c, with dev_c = x - mu_c, y_c = P_c dev_c, l_c = a_c - dev_c . y_c / 2:
+ *   log_p = logsumexp_c l_c,    score = - sum_c exp(l_c - log_p) y_c
+ * evaluated in log space (finite where the reference's sum of densities underflows).
+ * x: row-major (n, d) device array; log_coef (k): a_c = log w_c - (d log 2 pi + log det Sigma_c) / 2,
+ * -inf for a zero weight (the component contributes nothing); means (k, d) row-major; precision
+ * (k, d, d) row-major = np.linalg.inv(Sigma_c); all HOST-computed, on the DEVICE.  Writes log_p_out
+ * (n) and score_out (row-major (n, d)).  A row holding a NaN or an inf gets NaN outputs, no other
+ * row is affected.  A row's outputs depend only on that row and the parameters (not on n or the
+ * row's position).  Asynchronous on `stream`, allocates nothing.
+ * ST_ERR_INVALID: NULL (x and the outputs may be NULL when n == 0) or not 8-byte aligned pointers,
+ * n < 0, d < 1, k < 1.  ST_ERR_UNSUPPORTED: d > 64 or k > 1024.  n == 0: ST_OK, nothing enqueued.
+ * All checked before any HIP call.
+ * ---------------------------------------------------------------------------------------- */
+int st_mixture_logpdf_score(const double *x, int64_t n, int32_t d, int32_t k,
+                            const double *log_coef /* k: a_c */, const double *means /* (k, d) */,
+                            const double *precision /* (k, d, d) row-major */,
+                            double *log_p_out /* n */, double *score_out /* (n, d) row-major */,
+                            void *stream);
+
+/* ------------------------------------------------------------------------------------------
  * KDE proxy -- replaces jax.scipy.stats.gaussian_kde(sample.T, bw_method, weights).logpdf and its
  * jax.grad as the reference's Gaussian-mixture study feeds them to thin_gf (Gaussian_mixture.ipynb
  * cells 42-48, 51).  Whitened data p = x L (n points, SoA (d, ldp)) and queries q = y L (m points,
