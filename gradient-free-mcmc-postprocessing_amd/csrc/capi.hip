@@ -551,6 +551,30 @@ int st_mixture_logpdf_score(const double* x, int64_t n, int32_t d, int32_t k, co
     return hip_check(st::launch_mixture(a, static_cast<hipStream_t>(stream)), "mixture launch");
 }
 
+int64_t st_mvt_moments_workspace_bytes(int64_t n, int32_t d) {
+    if (n < 1 || d < 1 || d > st::kMvtMaxDim) return -1;
+    return st::mvt_moments_ws_bytes(n, d);
+}
+
+int st_mvt_moments(const double* x, int64_t n, int32_t d, const double* loc, const double* whiten, double df,
+                   int32_t want_grad, double* out, void* workspace, int64_t workspace_bytes, void* stream) {
+    if (n < 1) return fail(ST_ERR_INVALID, "n must be >= 1 (got %lld)", (long long)n);
+    if (d < 1) return fail(ST_ERR_INVALID, "d must be >= 1 (got %d)", d);
+    if (!(df > 0.0) || df == INFINITY) return fail(ST_ERR_INVALID, "df must be finite and > 0");
+    if (!x || !loc || !whiten || !out || !workspace) return fail(ST_ERR_INVALID, "NULL pointer");
+    const uintptr_t bits = reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(loc) |
+                           reinterpret_cast<uintptr_t>(whiten) | reinterpret_cast<uintptr_t>(out) |
+                           reinterpret_cast<uintptr_t>(workspace);
+    if (bits & 7u) return fail(ST_ERR_INVALID, "device arrays must be 8-byte aligned");
+    if (d > st::kMvtMaxDim)
+        return fail(ST_ERR_UNSUPPORTED, "d = %d exceeds the moment kernels' maximum %d", d, st::kMvtMaxDim);
+    if (workspace_bytes < st::mvt_moments_ws_bytes(n, d))
+        return fail(ST_ERR_INVALID, "workspace too small (%lld < %lld)", (long long)workspace_bytes,
+                    (long long)st::mvt_moments_ws_bytes(n, d));
+    st::MvtMomentsArgs a{x, loc, whiten, n, d, df, want_grad != 0, out, static_cast<double*>(workspace)};
+    return hip_check(st::launch_mvt_moments(a, static_cast<hipStream_t>(stream)), "mvt moments launch");
+}
+
 // accepted RK45 steps recorded per point by the two-phase gradient (typical: ~32 at the reference's
 // tolerances); a point that takes more is recomputed by the single-phase kernel
 constexpr int kLvStepCap = 64;

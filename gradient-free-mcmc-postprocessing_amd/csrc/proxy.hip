@@ -607,3 +607,4 @@ hipError_t launch_proxy(const ProxyArgs& a, hipStream_t s) {
 }  // namespace st
 
 #include "mixture.hpp"   // the Gaussian-mixture kernels: this file's tile constants and matrix-core lane maps
+#include "mvt_moments.hpp"   // the multivariate-t likelihood's sample moments: this file's tile constants

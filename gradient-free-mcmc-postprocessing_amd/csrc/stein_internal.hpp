@@ -145,6 +145,20 @@ struct MixtureArgs {
     double* score;           // row-major (n, d)
 };
 hipError_t launch_mixture(const MixtureArgs& a, hipStream_t s);   // csrc/mixture.hpp (in proxy.hip)
+constexpr int kMvtMaxDim = 16;         // the moment kernels' widest instantiation
+struct MvtMomentsArgs {
+    const double* x;     // row-major (n, d) raw sample
+    const double* loc;   // (d)
+    const double* U;     // (d, d) row-major whitening: z = (x - loc) @ U
+    int64_t n;
+    int d;
+    double df;           // > 0
+    int want_grad;       // 0: S0 only
+    double* out;         // S0, S1, Sz[d], Szz upper triangle row-major (want_grad = 0: out[0] only)
+    double* ws;          // mvt_moments_ws_bytes(n, d) bytes: one record per block
+};
+int64_t mvt_moments_ws_bytes(int64_t n, int d);                            // host only
+hipError_t launch_mvt_moments(const MvtMomentsArgs& a, hipStream_t s);     // csrc/mvt_moments.hpp (in proxy.hip)
 int dist_tune(int value);    // st_tune key 13 (energy kernel variant)
 
 struct LvArgs {

@@ -116,6 +116,8 @@ SIGNATURES = {
     'st_proxy_logpdf_grad': (ctypes.c_int, [_c_dp, _i64, _i32, _c_dp, _c_dp, _c_dp, _f64, _f64, _c_dp,
                                             _c_dp, _c_dp]),
     'st_mixture_logpdf_score': (ctypes.c_int, [_c_dp, _i64, _i32, _i32, _c_dp, _c_dp, _c_dp, _c_dp, _c_dp, _c_dp]),
+    'st_mvt_moments_workspace_bytes': (_i64, [_i64, _i32]),
+    'st_mvt_moments': (ctypes.c_int, [_c_dp, _i64, _i32, _c_dp, _c_dp, _f64, _i32, _c_dp, _c_dp, _i64, _c_dp]),
 }
 ABI_VERSION = 1
 

@@ -15,6 +15,13 @@ The reference builds the proxy q of ``thin_gf`` on the host before every gradien
   ``log_q = kde.logpdf(sample.T)``, ``gradient_q`` = jax.grad of it at every row
   (``kde_proxy``; O(n^2 d): csrc/kde.hip, ``st_kde_logpdf_grad``).
 
+* the fit of the Student-t proxy in the same notebook: ``fit_mvt`` / ``fit_mvt2`` (maximum likelihood under
+  ``scipy.optimize.minimize``, the objective ``-np.sum(stats.multivariate_t.logpdf(Y, loc, shape, df))``
+  differentiated by finite differences: 16 passes over the rows per gradient at d = 4) and
+  ``extract_t_params``.  Here (``StudentTLikelihood``, ``fit_mvt``, ``fit_mvt2``) one pass over the
+  device-resident rows gives the objective and its full analytic gradient (st_mvt_moments,
+  csrc/mvt_moments.hpp: the sums S0, S1, Sz, Szz; d <= 16).
+
 The parametric proxies are O(n d^2) per proxy (C5: n = 5e5, d = 50).  Here the d x d factors are computed on the host
 exactly as scipy does (``_PSD``: eigh, pseudo-inverse square root; ``np.linalg.inv``; the scalar
 constants in scipy's operation order) and the per-row work runs in one HIP kernel
@@ -24,6 +31,7 @@ order than NumPy/BLAS: log q and grad log q agree with scipy to fp64 rounding (t
 """
 from __future__ import annotations
 
+import ctypes
 import math
 from typing import Optional, Tuple
 
@@ -221,6 +229,231 @@ def thin_gf_t(sample, log_p, t_mu, t_scale, t_df, thinned_size: int, range_cap: 
     from .thinning import thin_gf
     log_q, gradient_q = student_t_proxy(sample, t_mu, t_scale, t_df)
     return thin_gf(sample, log_p, log_q, gradient_q, thinned_size, range_cap=range_cap)
+
+
+MVT_MAX_DIM = 16   # st_mvt_moments: the moment kernels' widest instantiation
+
+
+def _mvt_moments(lik: 'StudentTLikelihood', loc: np.ndarray, whiten: np.ndarray, df: float, want_grad: bool) -> np.ndarray:
+    """All the GPU work of a StudentTLikelihood: on first use the rows go to the device (a ROCm tensor is
+    used in place) with the workspace and the output; every call uploads loc and whiten (one small
+    copy), enqueues st_mvt_moments (two launches) and brings the 2 + d + d (d + 1) / 2 doubles back
+    (want_grad false: only S0 is computed; the rest of the record is stale)."""
+    import torch
+    n, d = lik.n, lik.d
+    st = lik._device
+    if st is None:
+        dev = nat.require_device()
+        x = lik.sample
+        if torch.is_tensor(x):
+            xd = x if x.is_contiguous() else x.contiguous()
+            if not bool(torch.isfinite(xd).all()):
+                raise ValueError('sample holds non-finite values')
+        else:
+            xd = torch.from_numpy(x if x.flags.writeable else x.copy()).to(dev)
+        wsb = int(nat.lib().st_mvt_moments_workspace_bytes(n, d))
+        if wsb < 0:
+            raise NotImplementedError(f'st_mvt_moments: d = {d} exceeds {MVT_MAX_DIM}')
+        st = lik._device = {
+            'x': xd,
+            'ws': torch.empty(wsb // 8, dtype=torch.float64, device=xd.device),
+            'out': torch.zeros(2 + d + d * (d + 1) // 2, dtype=torch.float64, device=xd.device),
+            'par': torch.empty(d + d * d, dtype=torch.float64, device=xd.device),
+            'host': np.empty(d + d * d),
+        }
+    host = st['host']
+    host[:d] = loc
+    host[d:] = np.asarray(whiten, dtype=np.float64).reshape(-1)
+    par = st['par']
+    par.copy_(torch.from_numpy(host))
+    with torch.cuda.device(par.device):
+        nat.check(nat.lib().st_mvt_moments(nat.ptr(st['x']), n, d, ctypes.c_void_p(par.data_ptr()),
+                                           ctypes.c_void_p(par.data_ptr() + 8 * d), float(df), 1 if want_grad else 0,
+                                           nat.ptr(st['out']), nat.ptr(st['ws']), st['ws'].numel() * 8,
+                                           nat.stream_handle()), 'st_mvt_moments')
+        return st['out'].cpu().numpy()
+
+
+class StudentTLikelihood:
+    """The multivariate-t likelihood of a sample with the rows resident on the GPU: the objective of
+    ``fit_mvt`` / ``fit_mvt2`` (Gradient_free_Student_t.ipynb: ``-np.sum(stats.multivariate_t.logpdf(Y,
+    loc, shape, df))``) and its analytic gradient from one pass over the rows (st_mvt_moments).
+
+    ``sample``: an (n, d) NumPy array or a float64 ROCm tensor (used in place), d <= 16, finite.  The
+    rows, the workspace and the output stay on the device for the object's lifetime; an evaluation is
+    two launches and one small copy each way."""
+
+    def __init__(self, sample):
+        tensor = hasattr(sample, 'data_ptr') and hasattr(sample, 'is_cuda')
+        if tensor:
+            import torch
+            if sample.dtype != torch.float64 or not sample.is_cuda:
+                raise ValueError('a tensor sample must be a float64 tensor on the ROCm device')
+            x = sample[:, None] if sample.ndim == 1 else sample
+        else:
+            x = np.ascontiguousarray(sample, dtype=np.float64)
+            x = x[:, None] if x.ndim == 1 else x
+        if x.ndim != 2:
+            raise ValueError(f'sample must be 2-d (n, d), got shape {tuple(x.shape)}')
+        self.n, self.d = int(x.shape[0]), int(x.shape[1])
+        if self.n < 1 or self.d < 1:
+            raise ValueError(f'sample must hold at least one row and one column, got shape {tuple(x.shape)}')
+        if self.d > MVT_MAX_DIM:
+            raise ValueError(f'd = {self.d} exceeds the moment kernels\' maximum {MVT_MAX_DIM}')
+        if not tensor and not np.all(np.isfinite(x)):
+            raise ValueError('sample holds non-finite values')
+        self.sample = x
+        self._device = None
+
+    def moments(self, loc, whiten, df: float, grad: bool = True):
+        """(S0, S1, Sz, Szz) as host doubles for z = (x - loc) @ whiten, delta = |z|^2, w = (df + d) /
+        (df + delta): S0 = sum log(1 + delta / df), S1 = sum w, Sz = sum w z (d), Szz = sum w z z^T
+        ((d, d), symmetric).  ``grad=False``: S0 alone (the same bits), the others None."""
+        d = self.d
+        loc = np.asarray(loc, dtype=np.float64).reshape(-1)
+        whiten = np.asarray(whiten, dtype=np.float64)
+        if loc.shape != (d,) or whiten.shape != (d, d):
+            raise ValueError(f'loc must have length {d} and whiten shape ({d}, {d})')
+        df = float(df)
+        if not df > 0 or not math.isfinite(df):
+            raise ValueError("'df' must be a finite number greater than zero")
+        if not (np.all(np.isfinite(loc)) and np.all(np.isfinite(whiten))):
+            raise ValueError('loc and whiten must be finite')
+        out = _mvt_moments(self, loc, whiten, df, bool(grad))
+        if not grad:
+            return float(out[0]), None, None, None
+        szz = np.zeros((d, d))
+        szz[np.triu_indices(d)] = out[2 + d:]
+        szz = szz + np.triu(szz, 1).T
+        return float(out[0]), float(out[1]), out[2:2 + d].copy(), szz
+
+    def _value_and_grads(self, loc, whiten, log_det: float, df: float, grad: bool):
+        """NLL for the shape with whitening ``whiten`` and log determinant ``log_det``; with ``grad``
+        also the moments and d NLL / d df."""
+        from scipy.special import gammaln, psi
+        n, d = self.n, self.d
+        s0, s1, sz, szz = self.moments(loc, whiten, df, grad)
+        c = gammaln(0.5 * (df + d)) - gammaln(0.5 * df) - d / 2. * np.log(df * np.pi) - 0.5 * log_det
+        value = -n * c + 0.5 * (df + d) * s0
+        if not grad:
+            return float(value), None
+        dc = 0.5 * psi(0.5 * (df + d)) - 0.5 * psi(0.5 * df) - d / (2. * df)
+        g_df = -n * dc + 0.5 * s0 - (df + d) / (2. * df) * (n - df * s1 / (df + d))
+        return float(value), (sz, szz, float(g_df))
+
+    def _split(self, par):
+        """fit_mvt's parameter vector -> (mu, A, inv(A), df); ValueError on a singular A."""
+        d = self.d
+        par = np.asarray(par, dtype=np.float64).reshape(-1)
+        if par.shape != (d + d * (d + 1) // 2 + 1,):
+            raise ValueError(f'par must have length {d + d * (d + 1) // 2 + 1}, got {par.shape[0]}')
+        a = np.zeros((d, d))
+        a[np.triu_indices(d)] = par[d:-1]
+        diag = np.diag(a)
+        if not np.all(np.isfinite(a)) or np.any(diag == 0.0):
+            raise ValueError('singular shape matrix: A has a zero on its diagonal')
+        from scipy.linalg import solve_triangular
+        u = np.triu(solve_triangular(a, np.eye(d), lower=False))
+        if not np.all(np.isfinite(u)):
+            raise ValueError('singular shape matrix: A cannot be inverted')
+        return par[:d], a, u, float(par[-1])
+
+    def nll(self, par) -> float:
+        """-sum multivariate_t.logpdf(sample, mu, A^T A, df) for par = [mu, triu(A), df]."""
+        mu, a, u, df = self._split(par)
+        log_det = 2.0 * np.sum(np.log(np.abs(np.diag(a))))
+        return self._value_and_grads(mu, u, log_det, df, False)[0]
+
+    def nll_and_grad(self, par):
+        """(value, gradient) of ``nll`` in the same parametrisation, from one pass over the rows."""
+        mu, a, u, df = self._split(par)
+        n, d = self.n, self.d
+        log_det = 2.0 * np.sum(np.log(np.abs(np.diag(a))))
+        value, (sz, szz, g_df) = self._value_and_grads(mu, u, log_det, df, True)
+        g_mu = -u @ sz
+        g_a = np.triu((n * np.eye(d) - szz) @ u.T)
+        return value, np.concatenate([g_mu, g_a[np.triu_indices(d)], [g_df]])
+
+    def nll_scaled(self, mu, whiten_c, log_det_c: float, s: float, df: float, grad: bool = True):
+        """fit_mvt2's objective: shape = exp(s) C with the fixed whitening ``whiten_c`` of C and its log
+        determinant; returns the value, or (value, [d / ds, d / d df])."""
+        n, d = self.n, self.d
+        value, g = self._value_and_grads(mu, math.exp(-0.5 * s) * np.asarray(whiten_c), d * s + log_det_c, df, grad)
+        if not grad:
+            return value
+        _, szz, g_df = g
+        return value, np.array([0.5 * (n * d - np.trace(szz)), g_df])
+
+
+def extract_t_params(par, d: int):
+    """(mu, scale, df) of fit_mvt's parameter vector [mu (d), triu(A) (np.triu_indices order), df]:
+    scale = A^T A (Gradient_free_Student_t.ipynb, extract_t_params)."""
+    par = np.asarray(par)
+    n_cov = d * (d + 1) // 2
+    a = np.zeros((d, d))
+    a[np.triu_indices(d)] = par[d:d + n_cov]
+    return par[:d], a.T @ a, par[d + n_cov]
+
+
+def _host_rows(sample) -> np.ndarray:
+    return sample.detach().cpu().numpy() if hasattr(sample, 'detach') else np.asarray(sample)
+
+
+def _check_jac(jac):
+    if jac not in ('analytic', None):
+        raise ValueError("jac must be 'analytic' or None")
+
+
+def fit_mvt(Y, mu_bounds, a_bounds, df_bounds, mu_init=None, df_init=4., method='L-BFGS-B', options=None,
+            jac='analytic'):
+    """Maximum-likelihood multivariate t of the rows of ``Y`` -- the notebook's ``fit_mvt`` (same start
+    vector: np.mean, the upper Cholesky factor of np.cov(Y, ddof=d), df_init; same bounds; the same
+    scipy.optimize.minimize call; returns its OptimizeResult) with the objective on the GPU.
+    ``jac='analytic'``: value and full gradient from one pass over the rows per evaluation (minimize's
+    jac=True); ``jac=None``: the value only, scipy differentiating by finite differences as the
+    reference does.  The rows are uploaded once per fit."""
+    from scipy.optimize import minimize
+    _check_jac(jac)
+    lik = Y if isinstance(Y, StudentTLikelihood) else StudentTLikelihood(Y)
+    rows = _host_rows(lik.sample)
+    d = lik.d
+    n_cov = d * (d + 1) // 2
+    if mu_init is None:
+        mu_init = np.mean(rows, axis=0)
+    sample_cov = np.atleast_2d(np.cov(rows, rowvar=False, ddof=d))
+    a = np.linalg.cholesky(sample_cov).T
+    start = np.concatenate([mu_init, a[np.triu_indices(d)], [df_init]])
+    lower = np.array([mu_bounds[0]] * d + [a_bounds[0]] * n_cov + [df_bounds[0]])
+    upper = np.array([mu_bounds[1]] * d + [a_bounds[1]] * n_cov + [df_bounds[1]])
+    bounds = list(zip(lower, upper))
+    if jac == 'analytic':
+        return minimize(lik.nll_and_grad, start, method=method, jac=True, bounds=bounds, options=options)
+    return minimize(lik.nll, start, method=method, bounds=bounds, options=options)
+
+
+def fit_mvt2(Y, scale_bounds, df_bounds, mu, scale_init=0.0, df_init=4., method='L-BFGS-B', options=None,
+             jac='analytic'):
+    """The notebook's ``fit_mvt2``: location ``mu`` fixed, shape = exp(scale) * np.cov(Y, ddof=d), the
+    parameters (scale, df); same start, bounds and minimize call, the objective on the GPU (``jac`` as
+    in ``fit_mvt``)."""
+    from scipy.linalg import solve_triangular
+    from scipy.optimize import minimize
+    _check_jac(jac)
+    lik = Y if isinstance(Y, StudentTLikelihood) else StudentTLikelihood(Y)
+    rows = _host_rows(lik.sample)
+    d = lik.d
+    mu = np.asarray(mu, dtype=np.float64).reshape(-1)
+    sample_cov = np.atleast_2d(np.cov(rows, rowvar=False, ddof=d))
+    a = np.linalg.cholesky(sample_cov).T                      # C = a^T a
+    whiten_c = np.triu(solve_triangular(a, np.eye(d), lower=False))
+    log_det_c = 2.0 * np.sum(np.log(np.diag(a)))
+    bounds = [scale_bounds, df_bounds]
+    start = np.array([scale_init, df_init])
+    if jac == 'analytic':
+        return minimize(lambda beta: lik.nll_scaled(mu, whiten_c, log_det_c, beta[0], beta[1], True), start,
+                        method=method, jac=True, bounds=bounds, options=options)
+    return minimize(lambda beta: lik.nll_scaled(mu, whiten_c, log_det_c, beta[0], beta[1], False), start,
+                    method=method, bounds=bounds, options=options)
 
 
 from .mixture import mixture_logpdf_score as mixture_proxy  # noqa: E402  (mixture.py imports _psd from here)

@@ -296,6 +296,28 @@ int st_mixture_logpdf_score(const double *x, int64_t n, int32_t d, int32_t k,
                             void *stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Sample moments of the multivariate-t likelihood -- what one evaluation of the objective of fit_mvt /
+ * fit_mvt2 (Gradient_free_Student_t.ipynb: -sum multivariate_t.logpdf(Y, loc, shape, df) under
+ * scipy.optimize.minimize) and of its analytic gradient needs from the rows.  With the whitening
+ * U (U U^T = inv(shape)), per row z = (x - loc) @ U, delta = |z|^2, w = (df + d) / (df + delta):
+ *   S0 = sum log(1 + (1 / df) delta),  S1 = sum w,  Sz = sum w z (d),  Szz = sum w z z^T (symmetric)
+ * x: row-major (n, d) device array (the caller's NumPy layout); loc (d) and whiten (d, d) row-major = U
+ * on the DEVICE.  out (device, 2 + d + d (d + 1) / 2 doubles): S0, S1, Sz[d], then the upper triangle
+ * of Szz row-major; want_grad = 0 computes and writes out[0] = S0 only, the same bits as want_grad = 1.
+ * Two launches on `stream` (per-block partial sums into the workspace, then one block adding them in
+ * block order): no atomics, the same inputs give the same bits on every call at a given grid (the
+ * grid follows n, the device's CU count and the st_tune grid cap, keys 5 / 23).  Allocates nothing.
+ * workspace: st_mvt_moments_workspace_bytes(n, d) bytes (host only; -1 if n < 1, d < 1 or d > 16).
+ * ST_ERR_INVALID: NULL or not 8-byte aligned pointers, n < 1, d < 1, df not finite or not > 0, a
+ * workspace that is too small.  ST_ERR_UNSUPPORTED: d > 16.  All checked before any HIP call.
+ * ---------------------------------------------------------------------------------------- */
+int64_t st_mvt_moments_workspace_bytes(int64_t n, int32_t d);
+int st_mvt_moments(const double *x, int64_t n, int32_t d, const double *loc, const double *whiten,
+                   double df, int32_t want_grad,
+                   double *out /* device: S0, S1, Sz[d], Szz upper triangle row-major */,
+                   void *workspace, int64_t workspace_bytes, void *stream);
+
+/* ------------------------------------------------------------------------------------------
  * KDE proxy -- replaces jax.scipy.stats.gaussian_kde(sample.T, bw_method, weights).logpdf and its
  * jax.grad as the reference's Gaussian-mixture study feeds them to thin_gf (Gaussian_mixture.ipynb
  * cells 42-48, 51).  Whitened data p = x L (n points, SoA (d, ldp)) and queries q = y L (m points,
