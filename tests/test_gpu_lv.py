@@ -5,7 +5,11 @@ the reference module itself (tests/golden/lv_reference.json, made by tests/golde
 Tolerance: scipy's RK45 takes the same steps as the kernel, but the stage combinations and dense
 output are BLAS dot products whose summation order differs, so values agree to rounding amplified
 by the integration (rtol 1e-8 here); a step-size decision that falls the other way on a last-bit
-difference would show as a ~1e-4 discrepancy and fail the test."""
+difference would show as a ~1e-4 discrepancy and fail the test.  tests/test_gpu_lv_edges.py checks that
+bound on the inputs held fixed here (covariance, tolerances, span, initial state, observation grid, theta
+wide enough to overflow the step table) and pins the recorded step table to scipy's sol.t; the reference's
+own reordering noise on those inputs, and their distance from a flipped step decision, are the constants
+RECORDED of tests/lv_ref.py (measured again by tests/test_lv_ref_cpu.py)."""
 import json
 import os
 
