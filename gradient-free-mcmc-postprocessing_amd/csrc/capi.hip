@@ -772,6 +772,93 @@ int st_distance_colsum_ws(const double* a_soa, int64_t lda, int64_t na, const do
                      "distance column-sum launch");
 }
 
+// ---- set-batched forms: one resident problem, many index sets (csrc/sets.hpp) ----------------------
+static bool aligned8(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 7u) == 0; }
+
+// the checks both entry points share, after the problem's own: rows, offsets, sizes
+static int check_sets(const int64_t* rows, const int64_t* set_offsets, int64_t n_sets) {
+    if (!rows || !set_offsets) return fail(ST_ERR_INVALID, "rows/set_offsets pointer is NULL");
+    if (!aligned8(rows) || !aligned8(set_offsets)) return fail(ST_ERR_INVALID, "rows/set_offsets must be 8-byte aligned");
+    switch (st::sets_check_offsets(set_offsets, n_sets)) {
+        case 1: return fail(ST_ERR_INVALID, "set_offsets[0] must be 0 (got %lld)", (long long)set_offsets[0]);
+        case 2: return fail(ST_ERR_INVALID, "set_offsets must not decrease");
+        case 3: return fail(ST_ERR_INVALID, "empty index set");
+        default: break;
+    }
+    if (n_sets > 0x7FFFFFFFll || st::sets_item_count(set_offsets, n_sets) > 0x7FFFFFFFll)
+        return fail(ST_ERR_UNSUPPORTED, "too many sets / column blocks for one grid");
+    return ST_OK;
+}
+
+int64_t st_sets_work_items(const int64_t* set_offsets, int64_t n_sets, int32_t* items_out, int64_t capacity) {
+    if (!set_offsets || n_sets < 0 || !aligned8(set_offsets)) return -1;
+    if (n_sets == 0) return 0;
+    if (st::sets_check_offsets(set_offsets, n_sets)) return -1;
+    const int64_t count = st::sets_item_count(set_offsets, n_sets);
+    if (n_sets > 0x7FFFFFFFll || count > 0x7FFFFFFFll) return -1;
+    if (items_out) {
+        if (capacity < count) return -1;
+        st::sets_build_items(set_offsets, n_sets, items_out);
+    }
+    return count;
+}
+
+int64_t st_ksd_sets_workspace_bytes(int64_t total_rows, int64_t n_sets, int32_t d) {
+    if (total_rows < 0 || n_sets < 0 || d < 1 || d > st::kMaxDim) return -1;
+    return st::sets_ws_bytes(total_rows, n_sets, 2 * d + 1);
+}
+
+int st_ksd_sets(const double* x_soa, const double* g_soa, const double* weights, int64_t n, int64_t ld,
+                int32_t d, double linv_scale, double linv_trace, const int64_t* rows,
+                const int64_t* set_offsets, int64_t n_sets, double* ks_out, double* csum_out,
+                void* workspace, int64_t workspace_bytes, void* stream) {
+    if (n_sets < 0) return fail(ST_ERR_INVALID, "n_sets must be >= 0 (got %lld)", (long long)n_sets);
+    if (n_sets == 0) return ST_OK;
+    int rc = check_problem(x_soa, g_soa, weights, n, d, ld);
+    if (rc) return rc;
+    rc = check_sets(rows, set_offsets, n_sets);
+    if (rc) return rc;
+    if (!ks_out || !workspace) return fail(ST_ERR_INVALID, "NULL output/workspace");
+    if (!aligned8(ks_out) || !aligned8(csum_out) || !aligned16(workspace))
+        return fail(ST_ERR_INVALID, "outputs must be 8-byte and the workspace 16-byte aligned");
+    if (workspace_bytes < st_ksd_sets_workspace_bytes(set_offsets[n_sets], n_sets, d))
+        return fail(ST_ERR_INVALID, "workspace too small");
+    st::PairArgs p{x_soa, g_soa, weights, ld, d, linv_scale, linv_trace};
+    return hip_check(st::launch_ksd_sets(p, n, rows, set_offsets, n_sets, ks_out, csum_out, workspace,
+                                         static_cast<hipStream_t>(stream)),
+                     "ksd sets launch");
+}
+
+int64_t st_distance_sets_workspace_bytes(int64_t total_rows, int64_t n_sets, int32_t d) {
+    if (total_rows < 0 || n_sets < 0 || d < 1 || d > st::kMaxDim) return -1;
+    return st::sets_ws_bytes(total_rows, n_sets, d);
+}
+
+int st_distance_sets(const double* p_soa, int64_t ldp, int64_t n, int32_t d, const int64_t* rows,
+                     const int64_t* set_offsets, int64_t n_sets, double* self_out, const double* row_values,
+                     double* segsum_out, void* workspace, int64_t workspace_bytes, void* stream) {
+    if (n_sets < 0) return fail(ST_ERR_INVALID, "n_sets must be >= 0 (got %lld)", (long long)n_sets);
+    if (n_sets == 0) return ST_OK;
+    if (!p_soa) return fail(ST_ERR_INVALID, "point pointer is NULL");
+    if (d < 1) return fail(ST_ERR_INVALID, "d must be >= 1 (got %d)", d);
+    if (d > st::kMaxDim) return fail(ST_ERR_UNSUPPORTED, "d = %d exceeds the supported maximum %d", d, st::kMaxDim);
+    if (n < 1 || ldp < n || (ldp & 7))
+        return fail(ST_ERR_INVALID, "bad sizes (ld must be a multiple of 8 and >= the row count)");
+    if (!aligned16(p_soa)) return fail(ST_ERR_INVALID, "device arrays must be 16-byte aligned");
+    int rc = check_sets(rows, set_offsets, n_sets);
+    if (rc) return rc;
+    if (!self_out || !workspace) return fail(ST_ERR_INVALID, "NULL output/workspace");
+    if ((segsum_out != nullptr) != (row_values != nullptr))
+        return fail(ST_ERR_INVALID, "row_values and segsum_out go together (both or neither)");
+    if (!aligned8(self_out) || !aligned8(row_values) || !aligned8(segsum_out) || !aligned16(workspace))
+        return fail(ST_ERR_INVALID, "arrays must be 8-byte and the workspace 16-byte aligned");
+    if (workspace_bytes < st_distance_sets_workspace_bytes(set_offsets[n_sets], n_sets, d))
+        return fail(ST_ERR_INVALID, "workspace too small");
+    return hip_check(st::launch_distance_sets(p_soa, ldp, n, d, rows, set_offsets, n_sets, self_out, row_values,
+                                              segsum_out, workspace, static_cast<hipStream_t>(stream)),
+                     "distance sets launch");
+}
+
 int st_kmat(const double* x_soa, const double* g_soa, const double* weights, int64_t k, int64_t ld,
             int32_t d, double linv_scale, double linv_trace, double* kmat_out, void* stream) {
     int rc = check_problem(x_soa, g_soa, weights, k, d, ld);

@@ -818,3 +818,5 @@ hipError_t launch_layout_soa_scaled(const double* rowmajor, int64_t n, int d, in
 }
 
 }  // namespace st
+
+#include "sets.hpp"   // set-batched KSD / distance sums: ragged triangles over many index sets

@@ -209,6 +209,16 @@ hipError_t launch_ksd_colsum(const PairArgs& p, int64_t n, int64_t a0, int64_t a
                              hipStream_t s);
 hipError_t launch_ksd_finish(const PairArgs& p, int64_t n, const double* csum, double* ks,
                              hipStream_t s);
+// set-batched forms (csrc/sets.hpp, in pairwise.hip): one resident problem, many index sets
+int sets_check_offsets(const int64_t* off, int64_t n_sets);     // host; 0 ok, 1 off[0] != 0, 2 decreasing, 3 empty set
+int64_t sets_item_count(const int64_t* off, int64_t n_sets);    // host: (set, column block) work items
+void sets_build_items(const int64_t* off, int64_t n_sets, int32_t* items);   // host: {set, block}, heaviest first
+int64_t sets_ws_bytes(int64_t total, int64_t n_sets, int nvec); // host: nvec SoA vectors per gathered row
+hipError_t launch_ksd_sets(const PairArgs& p, int64_t n, const int64_t* rows, const int64_t* set_offsets,
+                           int64_t n_sets, double* ks_out, double* csum_out, void* ws, hipStream_t s);
+hipError_t launch_distance_sets(const double* pts, int64_t ldp, int64_t n, int d, const int64_t* rows,
+                                const int64_t* set_offsets, int64_t n_sets, double* self_out,
+                                const double* row_values, double* segsum_out, void* ws, hipStream_t s);
 int64_t distance_chunks(int64_t na, int64_t b_begin, int64_t b_end);
 int dist_units_tune(int value);   // st_tune key 14
 int lv_tune(int value);           // st_tune key 17

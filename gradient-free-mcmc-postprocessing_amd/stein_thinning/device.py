@@ -27,6 +27,29 @@ def padded_ld(n: int) -> int:
     return max(PAD, ((n + PAD - 1) // PAD) * PAD)
 
 
+def concat_index_sets(index_sets, n: Optional[int] = None):
+    """(rows, offsets, sets) of a sequence of index sets: the sets concatenated in order (int64), the
+    n_sets + 1 offsets of the batched entry points, and the sets as 1-d arrays.  With ``n`` the indices
+    follow NumPy's rules for an axis of length n in ONE pass over the concatenation: negatives wrap,
+    out of range raises IndexError.  An empty set raises ValueError, a non-integer one IndexError."""
+    sets = [np.asarray(s).reshape(-1) for s in index_sets]
+    for k, s in enumerate(sets):
+        if s.size == 0:
+            raise ValueError(f'index set {k} is empty')
+        if s.dtype.kind not in 'iu':
+            raise IndexError(f'index set {k}: arrays used as indices must be of integer type')
+    offsets = np.zeros(len(sets) + 1, dtype=np.int64)
+    np.cumsum([s.shape[0] for s in sets], out=offsets[1:])
+    rows = np.concatenate(sets).astype(np.int64, copy=False) if sets else np.empty(0, dtype=np.int64)
+    if n is not None and rows.size:
+        lo, hi = int(rows.min()), int(rows.max())
+        if lo < -n or hi >= n:
+            raise IndexError(f'index {hi if hi >= n else lo} is out of bounds for axis 0 with size {n}')
+        if lo < 0:
+            rows = np.where(rows < 0, rows + n, rows)
+    return rows, offsets, sets
+
+
 class DedupView:
     """A problem's run starts as a compact DeviceProblem (DeviceProblem.dedup_view) and the maps
     between the two index spaces (the compaction keeps row order, so a lower index stays lower)."""
@@ -470,6 +493,48 @@ class DeviceProblem:
         nat.check(nat.lib().st_ksd_cumulative(
             nat.ptr(self.x), nat.ptr(self.g), nat.ptr(self.w), m, self.ld, self.d, self.l, self.tr,
             nat.ptr(ks), nat.ptr(ws), ws.numel() * 8, nat.stream_handle()), 'st_ksd_cumulative')
+        return ks.cpu().numpy()
+
+    def ksd_sets(self, rows, offsets, return_colsums: bool = False):
+        """KSD of many index sets over this problem's rows in one batched launch (st_ksd_sets): set s is
+        ``rows[offsets[s]:offsets[s + 1]]`` (row indices in [0, n), repeats allowed, the caller's order);
+        returns ks (n_sets,) with ks[s] = ``subset(set s).ksd(m_s)[-1]`` to rounding, and with
+        ``return_colsums`` also the concatenated column sums -- per set the bits of st_ksd_colsum on its
+        compact subset.  ``rows``: a host array or an int64 device tensor.  The number of launches and
+        copies does not depend on the number of sets.  Isotropic preconditioners only."""
+        import ctypes
+        import torch
+        if self.linv is not None:
+            raise NotImplementedError('ksd_sets: dense preconditioners take the per-set loop (stein.ksd_sets)')
+        off = np.ascontiguousarray(offsets, dtype=np.int64).reshape(-1)
+        n_sets = off.shape[0] - 1
+        if n_sets < 0:
+            raise ValueError('offsets must hold n_sets + 1 entries')
+        if n_sets == 0:
+            return (np.empty(0), np.empty(0)) if return_colsums else np.empty(0)
+        if isinstance(rows, torch.Tensor):
+            tr = rows.to(device=self.device, dtype=torch.int64).reshape(-1).contiguous()
+            bad = bool(((tr < 0) | (tr >= self.n)).any().item()) if tr.numel() else False
+        else:
+            hr = np.ascontiguousarray(rows, dtype=np.int64).reshape(-1)
+            bad = bool(hr.size and (hr.min() < 0 or hr.max() >= self.n))
+            tr = torch.from_numpy(hr).to(self.device)
+        if bad:
+            raise IndexError(f'row index out of bounds for a problem of {self.n} rows')
+        total = int(tr.shape[0])
+        if int(off[-1]) != total:
+            raise ValueError(f'offsets end at {int(off[-1])} but {total} rows were given')
+        L = nat.lib()
+        ws_bytes = int(L.st_ksd_sets_workspace_bytes(total, n_sets, self.d))
+        ws = torch.empty((ws_bytes + 15) // 16 * 2, dtype=torch.float64, device=self.device)
+        ks = torch.empty(n_sets, dtype=torch.float64, device=self.device)
+        cs = torch.empty(max(total, 1), dtype=torch.float64, device=self.device) if return_colsums else None
+        nat.check(L.st_ksd_sets(
+            nat.ptr(self.x), nat.ptr(self.g), nat.ptr(self.w), self.n, self.ld, self.d, self.l, self.tr,
+            nat.ptr(tr), off.ctypes.data_as(ctypes.c_void_p), n_sets, nat.ptr(ks), nat.ptr(cs), nat.ptr(ws),
+            ws.numel() * 8, nat.stream_handle()), 'st_ksd_sets')
+        if return_colsums:
+            return ks.cpu().numpy(), cs[:total].cpu().numpy()
         return ks.cpu().numpy()
 
     def kmat(self, k: int) -> np.ndarray:

@@ -21,7 +21,7 @@ from __future__ import annotations
 import numpy as np
 
 from . import _native as nat
-from .device import padded_ld
+from .device import concat_index_sets, padded_ld
 
 
 def _soa(points: np.ndarray, device):
@@ -181,3 +181,58 @@ def energy_distance_curve(reference_points, sample, idx, sizes) -> np.ndarray:
     if kmax > idx.shape[0] or (sizes.size and sizes.min() < 1):
         raise ValueError('sizes must lie in [1, len(idx)]')
     return EnergyCurve(reference_points, s[idx[:kmax]]).run(sizes)
+
+
+def distance_sets(soa, n: int, d: int, ld: int, rows, offsets: np.ndarray, row_values=None):
+    """One batched launch over index sets of a resident point set (st_distance_sets): ``soa`` (d, ld)
+    holds n points, set s is ``rows[offsets[s]:offsets[s + 1]]`` (``rows``: int64 device tensor, values in
+    [0, n)).  Returns device tensors (self_sums, segment_sums): per set, sum_{a<b} |p_a - p_b| over its
+    points and -- with ``row_values`` (n,) given, else None -- the sum of row_values over its rows.
+    The number of launches and copies does not depend on the number of sets."""
+    import ctypes
+    import torch
+    L = nat.lib()
+    offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+    n_sets, total = offsets.shape[0] - 1, int(rows.shape[0])
+    if int(offsets[-1]) != total:
+        raise ValueError(f'offsets end at {int(offsets[-1])} but {total} rows were given')
+    dev = soa.device
+    ws_bytes = int(L.st_distance_sets_workspace_bytes(total, n_sets, d))
+    ws = torch.empty((ws_bytes + 15) // 16 * 2, dtype=torch.float64, device=dev)
+    self_out = torch.empty(n_sets, dtype=torch.float64, device=dev)
+    seg = torch.empty(n_sets, dtype=torch.float64, device=dev) if row_values is not None else None
+    nat.check(L.st_distance_sets(nat.ptr(soa), ld, n, d, nat.ptr(rows), offsets.ctypes.data_as(ctypes.c_void_p),
+                                 n_sets, nat.ptr(self_out), nat.ptr(row_values), nat.ptr(seg), nat.ptr(ws),
+                                 ws.numel() * 8, nat.stream_handle()), 'st_distance_sets')
+    return self_out, seg
+
+
+def energy_distance_sets(reference_points, sample, index_sets) -> np.ndarray:
+    """sqrt(energy_distance(reference_points, sample[set])) for every index set -- the reference's
+    fit_quality of each naive-thinned subsample (``Gaussian_mixture.ipynb`` naive_st;
+    ``lotka_volterra/Comparison.ipynb`` rw_energy_distance_naive), which it evaluates with one dcor call
+    per thinned size -- in one pass: the reference set's self term from its ``PointSet`` (computed once),
+    the cross sums once per UNIQUE sample row (st_distance_colsum_ws), then every set's own triangle and
+    its segment of the cross sums in one batched launch (``distance_sets``).  Indices follow NumPy
+    (negatives wrap, IndexError out of range, repeats allowed); an empty set raises ValueError."""
+    import torch
+    s = _points(sample)
+    cat, offsets, sets = concat_index_sets(index_sets, s.shape[0])
+    if not sets:
+        return np.empty(0)
+    dev = nat.require_device()
+    ref = reference_points if isinstance(reference_points, PointSet) else point_set(reference_points, dev)
+    _check(ref.host, s)
+    sizes = np.diff(offsets)
+    used = np.zeros(s.shape[0], dtype=bool)
+    used[cat] = True
+    uniq = np.flatnonzero(used)                       # the rows any set uses, ascending
+    cat_u = (np.cumsum(used) - 1)[cat]                # the same rows as indices into uniq
+    us, nu, d, ldu = _soa(s[uniq], dev)
+    cross = _colsum(us, nu, ldu, ref.soa, ref.n, ref.ld, d, 0, ref.n, False, dev, host=False)
+    t_rows = torch.from_numpy(np.ascontiguousarray(cat_u, dtype=np.int64)).to(dev)
+    self_sums, seg = distance_sets(us, nu, d, ldu, t_rows, offsets, cross)
+    m = torch.from_numpy(sizes.astype(np.float64)).to(dev)
+    nx = float(ref.n)
+    ed = 2.0 * seg / (nx * m) - 2.0 * ref.self_sum() / (nx * nx) - 2.0 * self_sums / (m * m)
+    return torch.sqrt(ed).cpu().numpy()

@@ -19,6 +19,9 @@ Dispatch, for an integrand passed in:
   index arrays), summed in the reference's order;
 * any other callable (e.g. the matrix-lookup integrand of ``test_ksd.py``): the reference's protocol
   loop, one call per row, exactly as the reference issues them.
+
+``ksd_sets(integrand, index_sets)`` evaluates the final KSD of many arbitrary index sets (the
+reference's naive-thinning curve, one ``calculate_ksd`` per thinned size) in one batched launch.
 """
 from __future__ import annotations
 
@@ -233,3 +236,47 @@ def kmat(integrand: Callable, n: int) -> np.ndarray:
         res[i:, i] = row
     return res if res is not None else np.zeros((0, 0))
 
+
+
+def _reindexed(integrand: Callable, rows: np.ndarray) -> Callable:
+    """``integrand`` over rows ``rows``: the reference harness's reindex_integrand closure
+    (code/src/utils/ksd.py:9-16); a SteinIntegrand's own view where there is one."""
+    if isinstance(integrand, SteinIntegrand):
+        return integrand.reindex(rows)
+
+    def res(ind1, ind2):
+        return integrand(rows[ind1], rows[ind2])
+    return res
+
+
+def ksd_sets(integrand: Callable, index_sets) -> np.ndarray:
+    """KSD of each index set: element s equals
+    ``ksd(reindex_integrand(integrand, index_sets[s]), len(index_sets[s]))[-1]`` -- what the reference's
+    naive-thinning comparison evaluates with one ``calculate_ksd`` per thinned size
+    (``Gaussian_mixture.ipynb`` ksd_naive; ``lotka_volterra/Comparison.ipynb`` rw_ksd_naive).
+
+    The integrand is resolved as ``ksd`` resolves it: a ``SteinIntegrand``, its ``reindex`` view, or a
+    wrapper traced to ONE ``SteinIntegrand`` (over 1 + the largest index used) take ONE batched launch
+    whatever the number of sets (``DeviceProblem.ksd_sets``).  Indices follow NumPy: negatives wrap, out
+    of range raises IndexError, repeats are allowed.  Everything else -- dense preconditioners, wrappers
+    that do arithmetic, arbitrary callables, negative indices into a wrapper of unknown length -- is
+    the loop of per-set ``ksd(...)[-1]``.  An empty set raises ValueError; no sets give an empty array."""
+    from .device import concat_index_sets
+    index_sets = list(index_sets)
+    base = None
+    if isinstance(integrand, SteinIntegrand):
+        rows, offsets, sets = concat_index_sets(index_sets, integrand.n)
+        if sets and integrand.linv_dense is None:
+            base = (integrand.base(), rows if integrand._rows is None else integrand._rows[rows])
+    else:
+        rows, offsets, sets = concat_index_sets(index_sets)
+        inner = _inner_integrand(integrand)
+        if sets and inner is not None and inner.linv_dense is None and int(rows.min()) >= 0:
+            dev = _device_rows(integrand, 1 + int(rows.max()))
+            if dev is not None:
+                base = (dev[0], dev[0].base_rows(dev[1][rows]))
+    if not sets:
+        return np.empty(0)
+    if base is None:
+        return np.array([ksd(_reindexed(integrand, s), s.shape[0])[-1] for s in sets], dtype=np.float64)
+    return base[0].base_problem().ksd_sets(base[1], offsets)

@@ -410,6 +410,54 @@ int st_kmat(const double *x_soa, const double *g_soa, const double *weights, int
             void *stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Set-batched KSD and distance sums -- ONE resident problem, n_sets arbitrary index sets over its
+ * rows, one result per set: the reference's naive-thinning curves, whose index sets
+ * np.linspace(0, n - 1, m).astype(int) are not nested (Gaussian_mixture.ipynb ksd_naive / naive_st,
+ * m = 1..1000; lotka_volterra/Comparison.ipynb rw_ksd_naive / rw_energy_distance_naive over
+ * thinned_sizes), evaluated there as one full KSD / energy distance per size.
+ * rows (DEVICE, total_rows = set_offsets[n_sets] int64): the sets' row indices, each in [0, n),
+ * concatenated in the caller's order (repeats allowed; the caller validates the range -- a row outside
+ * it is never dereferenced and makes its set's results NaN).  set_offsets (HOST, n_sets + 1 int64):
+ * set s is rows[set_offsets[s] .. set_offsets[s+1]); read only during the call.
+ *   st_ksd_sets:       csum_out[j] = sum_{a < j, same set} k(r_j, r_a) ((k w_j) w_a with weights), in the
+ *                      concatenated order -- for each set the bits of st_ksd_colsum on its compact
+ *                      subset -- and ks_out[s] = sqrt(sum_j (2 csum[j] + k(r_j, r_j))) / m_s, i.e.
+ *                      stein.ksd(reindex_integrand(integrand, set), m_s)[-1].  csum_out may be NULL.
+ *   st_distance_sets:  self_out[s] = sum_{a < b} |p_a - p_b| over the set's points (K7's distance); with
+ *                      row_values (device, n) and segsum_out both given, segsum_out[s] = sum over the
+ *                      set's rows of row_values[row] (per-row cross sums computed once per unique row
+ *                      with st_distance_colsum_ws); both NULL: skipped.
+ * A fixed number of launches and ONE host-to-device copy (offsets + work-item table) whatever n_sets is.
+ * Work items are (set, block of 256 columns) pairs, heaviest first (st_sets_work_items); per column a
+ * sequential sum in increasing a; per set, thread t of one block adds columns t, t + 256, ... and a
+ * fixed binary tree joins the 256 partials: the order depends on m_s only.  No atomics, the same
+ * inputs give the same bits.  Nothing waits on the host except that the table is copied from ordinary
+ * host memory, which the runtime has read when the call returns.  Allocates no device memory.
+ * workspace: st_*_sets_workspace_bytes(total_rows, n_sets, d) bytes (host only; -1 for bad arguments).
+ * ST_ERR_INVALID: NULL or misaligned pointers (device arrays 16, index / output arrays 8 bytes),
+ * n_sets < 0, offsets not starting at 0 or decreasing, an empty set, a workspace that is too small.
+ * ST_ERR_UNSUPPORTED: d > 128.  All checked before any HIP call.  n_sets == 0: ST_OK, nothing done.
+ *   st_sets_work_items: host only -- the work-item table of these offsets: items_out[2 q] = set,
+ *     items_out[2 q + 1] = column block of item q, non-increasing in the block's pair count.  Returns
+ *     the item count (items_out NULL: count only), -1 for invalid offsets or capacity < count.
+ * ---------------------------------------------------------------------------------------- */
+int64_t st_sets_work_items(const int64_t *set_offsets, int64_t n_sets, int32_t *items_out, int64_t capacity);
+int64_t st_ksd_sets_workspace_bytes(int64_t total_rows, int64_t n_sets, int32_t d);
+int st_ksd_sets(const double *x_soa, const double *g_soa, const double *weights, int64_t n, int64_t ld,
+                int32_t d, double linv_scale, double linv_trace,
+                const int64_t *rows /* device, total_rows */,
+                const int64_t *set_offsets /* HOST, n_sets + 1 */, int64_t n_sets,
+                double *ks_out /* device, n_sets */, double *csum_out /* device, total_rows, or NULL */,
+                void *workspace, int64_t workspace_bytes, void *stream);
+int64_t st_distance_sets_workspace_bytes(int64_t total_rows, int64_t n_sets, int32_t d);
+int st_distance_sets(const double *p_soa, int64_t ldp, int64_t n, int32_t d,
+                     const int64_t *rows /* device, total_rows */,
+                     const int64_t *set_offsets /* HOST, n_sets + 1 */, int64_t n_sets,
+                     double *self_out /* device, n_sets */, const double *row_values /* device, n, or NULL */,
+                     double *segsum_out /* device, n_sets, or NULL */,
+                     void *workspace, int64_t workspace_bytes, void *stream);
+
+/* ------------------------------------------------------------------------------------------
  * Dense preconditioners -- Gamma^-1 = L, any symmetric positive-definite (d, d) matrix, d <= 16 (the
  * reference's vfk0_imq takes any linv; upstream's preconditioner='smpcov' is the inverse sample
  * covariance).  Each function takes the arguments of its isotropic twin with linv_scale replaced by
