@@ -105,6 +105,7 @@ int st_tune(int32_t key, int32_t value) {
     else if (key == 14) rc = st::dist_units_tune(value);
     else if (key == 17) rc = st::lv_tune(value);
     else if (key == 18) rc = st::lv_pieces_tune(value);
+    else if (key == 24) rc = st::kde_t_tune(value);
     else rc = ((key >= 3 && key <= 5) || key == 8 || key == 9 || key == 10 || key == 12 || key == 15 || key == 16 ||
                key == 19 || key == 23)
                   ? st::persistent_tune(key, value)
@@ -514,6 +515,30 @@ int st_kde_logpdf_grad(const double* p_soa, int64_t ldp, int64_t n, const double
                                     whiten, log_q_out, grad_out, static_cast<double*>(workspace),
                                     static_cast<hipStream_t>(stream)),
                      "kde launch");
+}
+
+int64_t st_kde_t_workspace_bytes(int64_t m, int32_t d) {
+    if (m < 0 || d < 1 || d > st::kMaxDim) return -1;
+    return st::kde_workspace_bytes(m, d);
+}
+
+int st_kde_t_logpdf_grad(const double* p_soa, int64_t ldp, int64_t n, const double* log_weights,
+                         double log_weight_uniform, const double* q_soa, int64_t ldq, int64_t m, int32_t d,
+                         double df, double log_norm, const double* whiten, double* log_q_out, double* grad_out,
+                         void* workspace, int64_t workspace_bytes, void* stream) {
+    if (m == 0) return ST_OK;
+    if (!p_soa || !q_soa || !whiten || !log_q_out || !grad_out) return fail(ST_ERR_INVALID, "NULL pointer");
+    if (n < 1 || m < 0 || ldp < n || ldq < m) return fail(ST_ERR_INVALID, "bad sizes (need n >= 1, ld >= count)");
+    if (!(df > 0.0) || df == INFINITY) return fail(ST_ERR_INVALID, "df must be finite and > 0");
+    if (d < 1 || d > st::kMaxDim) return fail(ST_ERR_UNSUPPORTED, "unsupported d = %d", d);
+    if ((m + 255) / 256 > 0x7FFFFFFFll) return fail(ST_ERR_UNSUPPORTED, "m too large");
+    if (workspace_bytes < st::kde_workspace_bytes(m, d) || (st::kde_workspace_bytes(m, d) > 0 && !workspace))
+        return fail(ST_ERR_INVALID, "workspace too small (%lld < %lld)", (long long)workspace_bytes,
+                    (long long)st::kde_workspace_bytes(m, d));
+    return hip_check(st::launch_kde_t(p_soa, ldp, n, log_weights, log_weight_uniform, q_soa, ldq, m, d, df,
+                                      log_norm, whiten, log_q_out, grad_out, static_cast<double*>(workspace),
+                                      static_cast<hipStream_t>(stream)),
+                     "kde_t launch");
 }
 
 int st_proxy_logpdf_grad(const double* x, int64_t n, int32_t d, const double* loc,

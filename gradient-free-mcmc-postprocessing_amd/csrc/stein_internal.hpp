@@ -129,6 +129,11 @@ int64_t kde_workspace_bytes(int64_t m, int d);
 hipError_t launch_kde(const double* p, int64_t ldp, int64_t n, const double* logw, double logw0,
                       const double* q, int64_t ldq, int64_t m, int d, double log_norm, const double* L,
                       double* log_q, double* grad, double* ws, hipStream_t s);
+// Student-t kernel density (same workspace as launch_kde); log_norm = log_norm_t of the header
+hipError_t launch_kde_t(const double* p, int64_t ldp, int64_t n, const double* logw, double logw0,
+                        const double* q, int64_t ldq, int64_t m, int d, double df, double log_norm,
+                        const double* L, double* log_q, double* grad, double* ws, hipStream_t s);
+int kde_t_tune(int value);   // st_tune key 24 (power path of the Student-t KDE)
 hipError_t launch_proxy(const ProxyArgs& a, hipStream_t s);
 int proxy_tune(int value);   // st_tune key 7
 constexpr int kMixtureMaxDim = 64;     // the matrix-core kernel's widest instantiation

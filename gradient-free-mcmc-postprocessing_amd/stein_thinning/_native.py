@@ -103,6 +103,9 @@ SIGNATURES = {
     'st_kde_workspace_bytes': (_i64, [_i64, _i32]),
     'st_kde_logpdf_grad': (ctypes.c_int, [_c_dp, _i64, _i64, _c_dp, _f64, _c_dp, _i64, _i64, _i32, _f64, _c_dp,
                                           _c_dp, _c_dp, _c_dp, _i64, _c_dp]),
+    'st_kde_t_workspace_bytes': (_i64, [_i64, _i32]),
+    'st_kde_t_logpdf_grad': (ctypes.c_int, [_c_dp, _i64, _i64, _c_dp, _f64, _c_dp, _i64, _i64, _i32, _f64, _f64,
+                                            _c_dp, _c_dp, _c_dp, _c_dp, _i64, _c_dp]),
     # dense preconditioner: the isotropic twin's arguments with linv_scale replaced by the (d, d) device array
     'st_greedy_dense': (ctypes.c_int, [_c_dp, _c_dp, _c_dp, _i64, _i32, _i64, _c_dp, _f64, _i64,
                                        _c_dp, _c_dp, _c_dp, _i64, _c_dp]),

@@ -15,6 +15,9 @@ The reference builds the proxy q of ``thin_gf`` on the host before every gradien
   ``log_q = kde.logpdf(sample.T)``, ``gradient_q`` = jax.grad of it at every row
   (``kde_proxy``; O(n^2 d): csrc/kde.hip, ``st_kde_logpdf_grad``).
 
+* beyond the reference (its report's "Further Work": KDE kernels other than Gaussian): the Student-t
+  kernel density ``kde_t_proxy`` / ``kde_t_thin`` (``st_kde_t_logpdf_grad``).
+
 * the fit of the Student-t proxy in the same notebook: ``fit_mvt`` / ``fit_mvt2`` (maximum likelihood under
   ``scipy.optimize.minimize``, the objective ``-np.sum(stats.multivariate_t.logpdf(Y, loc, shape, df))``
   differentiated by finite differences: 16 passes over the rows per gradient at d = 4) and
@@ -167,44 +170,145 @@ def kde_factors(dataset, bw_method='silverman', weights=None):
     return w, L, log_norm
 
 
-def kde_proxy(sample, points=None, bw_method='silverman', weights=None) -> Tuple[np.ndarray, np.ndarray]:
+def kde_t_factors(dataset, df, bw_method='silverman', weights=None):
+    """``kde_factors`` for the Student-t kernel density: the same normalised weights and whitening factor L
+    (the Gaussian KDE's bandwidth rule, unchanged) and the kernel's log normaliser
+
+        log_norm_t = sum(log diag L) + gammaln((df + d) / 2) - gammaln(df / 2) - d / 2 log(df pi),
+
+    so that the density is sum_i w_i multivariate_t(y; loc = x_i, shape = cov * factor^2, df).  Returns
+    (weights, L, log_norm_t).  For df >> 1e7 the two gammaln terms cancel to a few digits in float64 (their
+    difference is ~ d / 2 log(df / 2) against values ~ df log df): the Gaussian limit is better served by
+    ``kde_proxy`` itself."""
+    from scipy.special import gammaln
+    df = float(df)
+    if not df > 0 or not math.isfinite(df):
+        raise ValueError("'df' must be a finite number greater than zero")
+    w, L, _ = kde_factors(dataset, bw_method, weights)
+    d = L.shape[0]
+    log_norm_t = float(np.sum(np.log(np.diag(L))) + gammaln(0.5 * (df + d)) - gammaln(0.5 * df)
+                       - 0.5 * d * np.log(df * np.pi))
+    return w, L, log_norm_t
+
+
+def collapse_rows(rows, weights=None):
+    """Repeated rows collapsed (an RW chain repeats its row at every rejection): ``(unique, summed, inverse)``
+    with ``unique`` the distinct rows (np.unique's order), ``summed`` the sum of ``weights`` over each one's
+    copies (None when ``weights`` is None) and ``inverse`` the index of every input row in ``unique``."""
+    rows = np.asarray(rows, dtype=np.float64)
+    unique, inverse = np.unique(rows, axis=0, return_inverse=True)
+    inverse = np.asarray(inverse).reshape(-1)
+    summed = None if weights is None else np.bincount(inverse, weights=weights, minlength=unique.shape[0])
+    return unique, summed, inverse
+
+
+def _kde_eval(data, pts, w, weighted, L, log_norm, df, collapse_repeats):
+    """The GPU part of kde_proxy (df None: st_kde_logpdf_grad) and kde_t_proxy (st_kde_t_logpdf_grad): data
+    and queries whitened with L and uploaded, log q and its gradient at every row of ``pts`` back on the
+    host.  ``w`` are the normalised weights of the full data set (used when ``weighted`` or when rows are
+    collapsed: a unique row then carries the log of its copies' summed weight)."""
+    import torch
+    from .device import padded_ld
+    n, d = data.shape
+    m = pts.shape[0]
+    dev = nat.require_device()
+    if m == 0:
+        return np.empty(0), np.empty((0, d))
+    inverse = None
+    if collapse_repeats:
+        same = pts is data
+        data, w, inv_d = collapse_rows(data, w)
+        weighted = True
+        if same:
+            pts, inverse = data, inv_d
+        else:
+            pts, _, inverse = collapse_rows(pts)
+        n, m = data.shape[0], pts.shape[0]
+    log_q = torch.empty(m, dtype=torch.float64, device=dev)
+    grad = torch.empty((m, d), dtype=torch.float64, device=dev)
+
+    def soa(a):
+        ld = padded_ld(a.shape[0])
+        t = torch.zeros((d, ld), dtype=torch.float64, device=dev)
+        t[:, :a.shape[0]] = torch.from_numpy(np.ascontiguousarray((a @ L).T)).to(dev)   # whitened: a @ L
+        return t, ld
+    p_t, ldp = soa(data)
+    q_t, ldq = soa(pts)
+    logw = torch.from_numpy(np.log(w)).to(dev) if weighted else None   # a zero weight: -inf (NumPy warns)
+    lt = torch.from_numpy(np.ascontiguousarray(L)).to(dev)
+    lib = nat.lib()
+    if df is None:
+        wsb = int(lib.st_kde_workspace_bytes(m, d))
+        ws = torch.empty(max(wsb // 8, 2), dtype=torch.float64, device=dev)
+        nat.check(lib.st_kde_logpdf_grad(nat.ptr(p_t), ldp, n, nat.ptr(logw), float(np.log(1.0 / n)),
+                                         nat.ptr(q_t), ldq, m, d, log_norm, nat.ptr(lt), nat.ptr(log_q),
+                                         nat.ptr(grad), nat.ptr(ws), ws.numel() * 8, nat.stream_handle()),
+                  'st_kde_logpdf_grad')
+    else:
+        wsb = int(lib.st_kde_t_workspace_bytes(m, d))
+        ws = torch.empty(max(wsb // 8, 2), dtype=torch.float64, device=dev)
+        nat.check(lib.st_kde_t_logpdf_grad(nat.ptr(p_t), ldp, n, nat.ptr(logw), float(np.log(1.0 / n)),
+                                           nat.ptr(q_t), ldq, m, d, float(df), log_norm, nat.ptr(lt),
+                                           nat.ptr(log_q), nat.ptr(grad), nat.ptr(ws), ws.numel() * 8,
+                                           nat.stream_handle()),
+                  'st_kde_t_logpdf_grad')
+    log_q, grad = log_q.cpu().numpy(), grad.cpu().numpy()
+    if inverse is not None:
+        log_q, grad = log_q[inverse], grad[inverse]
+    return log_q, grad
+
+
+def _kde_inputs(sample, points):
+    data = np.asarray(sample, dtype=np.float64)
+    data = data[:, None] if data.ndim == 1 else data
+    if points is None:
+        return data, data
+    pts = np.asarray(points, dtype=np.float64)
+    pts = pts[:, None] if pts.ndim == 1 else pts
+    if pts.ndim != 2 or pts.shape[1] != data.shape[1]:
+        raise ValueError(f'points must be (m, {data.shape[1]})')
+    return data, pts
+
+
+def kde_proxy(sample, points=None, bw_method='silverman', weights=None,
+              collapse_repeats=False) -> Tuple[np.ndarray, np.ndarray]:
     """(log_q, gradient_q) of the Gaussian KDE of ``sample`` at ``points`` (default: the sample
     itself) -- ``gaussian_kde(sample.T, bw_method, weights).logpdf(points.T)`` and its gradient, as
     Gaussian_mixture.ipynb cells 46-48 / 51 compute them for thin_gf.  The O(n m d) pair sums run
     on the GPU (st_kde_logpdf_grad); agrees with the restatement to fp64 rounding (the
-    logsumexp and the softmax-weighted sums are sequential here, pairwise in NumPy)."""
-    import torch
-    from .device import padded_ld
-    data = np.asarray(sample, dtype=np.float64)
-    data = data[:, None] if data.ndim == 1 else data
-    pts = data if points is None else np.asarray(points, dtype=np.float64)
-    pts = pts[:, None] if pts.ndim == 1 else pts
-    n, d = data.shape
-    if pts.ndim != 2 or pts.shape[1] != d:
-        raise ValueError(f'points must be (m, {d})')
-    m = pts.shape[0]
+    logsumexp and the softmax-weighted sums are sequential here, pairwise in NumPy).
+
+    ``collapse_repeats=True``: repeated rows (an RW chain's rejections) are sent to the kernel once -- a
+    unique data row carries the log of its copies' summed weight, a unique query row is evaluated once and
+    scattered back.  The bandwidth factors still come from the full data set; the result differs from the
+    uncollapsed one by the rounding of the reordered sums."""
+    data, pts = _kde_inputs(sample, points)
     w, L, log_norm = kde_factors(data, bw_method, weights)
-    dev = nat.require_device()
-    log_q = torch.empty(max(m, 1), dtype=torch.float64, device=dev)
-    grad = torch.empty((max(m, 1), d), dtype=torch.float64, device=dev)
-    if m:
-        def soa(a):
-            ld = padded_ld(a.shape[0])
-            t = torch.zeros((d, ld), dtype=torch.float64, device=dev)
-            t[:, :a.shape[0]] = torch.from_numpy(np.ascontiguousarray((a @ L).T)).to(dev)   # whitened: a @ L
-            return t, ld
-        p_t, ldp = soa(data)
-        q_t, ldq = soa(pts)
-        uniform = weights is None
-        logw = None if uniform else torch.from_numpy(np.log(w)).to(dev)
-        lt = torch.from_numpy(np.ascontiguousarray(L)).to(dev)
-        wsb = int(nat.lib().st_kde_workspace_bytes(m, d))
-        ws = torch.empty(max(wsb // 8, 2), dtype=torch.float64, device=dev)
-        nat.check(nat.lib().st_kde_logpdf_grad(nat.ptr(p_t), ldp, n, nat.ptr(logw), float(np.log(1.0 / n)),
-                                               nat.ptr(q_t), ldq, m, d, log_norm, nat.ptr(lt), nat.ptr(log_q),
-                                               nat.ptr(grad), nat.ptr(ws), ws.numel() * 8, nat.stream_handle()),
-                  'st_kde_logpdf_grad')
-    return log_q[:m].cpu().numpy(), grad[:m].cpu().numpy()
+    return _kde_eval(data, pts, w, weights is not None, L, log_norm, None, collapse_repeats)
+
+
+def kde_t_proxy(sample, points=None, df=4.0, bw_method='silverman', weights=None,
+                collapse_repeats=False) -> Tuple[np.ndarray, np.ndarray]:
+    """(log_q, gradient_q) of the Student-t kernel density of ``sample`` at ``points`` (default: the sample
+    itself): q = sum_i w_i multivariate_t(y; loc = x_i, shape = cov * factor^2, df) with the polynomial
+    tails the Gaussian KDE lacks (far from the data log q falls like -(df + d) log r, not -r^2 / 2) and a
+    closed-form score.  Conventions as ``kde_proxy`` (1-D input is a column; ``collapse_repeats``).  The
+    bandwidth is the Gaussian KDE's rule (``bw_method``: 'scott', 'silverman' or a scalar factor on the
+    weighted data covariance) applied unchanged to the t kernel's shape matrix: a choice made here, not
+    something the reference pins (it evaluates no KDE kernel other than the Gaussian).  The pair sums run
+    on the GPU (st_kde_t_logpdf_grad, csrc/kde.hip)."""
+    data, pts = _kde_inputs(sample, points)
+    w, L, log_norm_t = kde_t_factors(data, df, bw_method, weights)
+    return _kde_eval(data, pts, w, weights is not None, L, log_norm_t, float(df), collapse_repeats)
+
+
+def kde_t_thin(sample, log_p, thinned_size: int, df=4.0, bw_method='silverman',
+               range_cap: Optional[float] = 200, collapse_repeats=True) -> np.ndarray:
+    """``gaussian_thin`` with the Student-t kernel density of the sample itself as the proxy
+    (``kde_t_proxy``), then ``thin_gf(..., preconditioner='med')``."""
+    from .thinning import thin_gf
+    log_q, gradient_q = kde_t_proxy(sample, None, df, bw_method, collapse_repeats=collapse_repeats)
+    return thin_gf(sample, log_p, log_q, gradient_q, thinned_size, range_cap=range_cap, preconditioner='med')
 
 
 def gaussian_thin(sample, log_p, mean, cov, thinned_size: int, range_cap: Optional[float] = 200) -> np.ndarray:

@@ -98,7 +98,10 @@ int64_t st_greedy_workspace_bytes(int64_t n, int32_t d, int32_t nranks);
  * arithmetic (1 / -1 = on, the default; 0 = off; see st_greedy_near_tie; same indices and sums), key 22 = key 11 for the
  * launches of the CALLING HOST THREAD only (-1 = none: key 11 applies; 0 / 1 as key 11) -- the library keeps
  * it per thread, so threads thinning side by side (one per GPU) never change each other's arithmetic, key
- * 23 = key 5 for the calling host thread only (-1 = none; 1..512 blocks).
+ * 23 = key 5 for the calling host thread only (-1 = none; 1..512 blocks), key 24 = power path of the
+ * Student-t KDE (st_kde_t_logpdf_grad): 0 / -1 = automatic (a multiplication chain when df + d is an integer
+ * of at most 256, exp(h log) otherwise), 1 = exp(h log) for every df, 2 = the chain with a run-time exponent for
+ * every df (d <= 8: no sweep compiled for the exponent) -- the two A/Bs of DESIGN.md; within rounding.
  */
 int st_tune(int32_t key, int32_t value);
 
@@ -332,6 +335,27 @@ int st_kde_logpdf_grad(const double *p_soa, int64_t ldp, int64_t n, const double
                        double log_weight_uniform, const double *q_soa, int64_t ldq, int64_t m, int32_t d,
                        double log_norm, const double *whiten, double *log_q_out, double *grad_out,
                        void *workspace, int64_t workspace_bytes, void *stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Student-t KDE proxy -- the KDE above with the fat-tailed kernel multivariate_t(y; loc = x_i, shape =
+ * the KDE's covariance, df) in place of the Gaussian one (the report's "Further Work": KDE kernels other
+ * than Gaussian).  Same layout and conventions as st_kde_logpdf_grad, with df added; log_norm is
+ *   log_norm_t = sum(log diag L) + lgamma((df + d) / 2) - lgamma(df / 2) - d / 2 log(df pi)   (HOST):
+ *   log_q[j] = logsumexp_i(log w_i + log_norm_t - (df + d) / 2 log(1 + |p_i - q_j|^2 / df)),
+ *   grad[j]  = (sum_i softmax_i(.) (df + d) / (df + |p_i - q_j|^2) (p_i - q_j)) L^T   (row-major (m, d)).
+ * A log weight of -inf drops its point out exactly (its coordinates are not used); all of them -inf gives
+ * log_q = -inf.  Nothing underflows where the result is finite, for non-zero weights spanning a ratio of
+ * at most 2^900 (the per-query shift is the nearest weighted point and the largest weight; csrc/kde.hip).
+ * Deterministic (sums sequential in i, no atomics).  m = 0 is a no-op.
+ * workspace: st_kde_t_workspace_bytes(m, d) bytes (0 for d <= 8; -1 if m < 0 or d outside 1 .. 128).
+ * ST_ERR_INVALID: NULL pointers, n < 1, m < 0, ldp < n, ldq < m, df not finite or not > 0, a workspace
+ * that is too small.  ST_ERR_UNSUPPORTED: d outside 1 .. 128.  All checked before any HIP call.
+ * ---------------------------------------------------------------------------------------- */
+int64_t st_kde_t_workspace_bytes(int64_t m, int32_t d);
+int st_kde_t_logpdf_grad(const double *p_soa, int64_t ldp, int64_t n, const double *log_weights,
+                         double log_weight_uniform, const double *q_soa, int64_t ldq, int64_t m, int32_t d,
+                         double df, double log_norm, const double *whiten, double *log_q_out, double *grad_out,
+                         void *workspace, int64_t workspace_bytes, void *stream);
 
 /* ------------------------------------------------------------------------------------------
  * Lotka-Volterra inputs, batched over n parameter points (one RK45 integration per point, scipy's
