@@ -11,7 +11,9 @@
 //     grad  = (-(df + d) / df) / (1 + m / df) * (inv(shape) @ (x - loc)),   m = (x-loc).inv(shape).(x-loc)
 // U is scipy's _PSD factor (U U^T = pinv(cov)), computed on the host like the reference does; P =
 // np.linalg.inv(cov).  Constant parts are computed on the host with the reference's operation order;
-// the per-row dot products differ from NumPy/BLAS in summation order only (fp64 tolerance).
+// the VALU kernel's per-row dot products differ from NumPy/BLAS in summation order only (fp64
+// rounding).  The matrix-core kernels (16 < d <= 64) evaluate the Mahalanobis term as dev . P dev
+// instead of |dev @ U|^2: see the note above proxy_mfma_kernel for what that agrees with scipy to.
 //
 // Layout: x, grad row-major (n, d) exactly as the caller's NumPy arrays; one block = 64 rows
 // (lane = row) x 4 waves (column groups).  The block stages its (64, d) tile of x - loc transposed
@@ -140,13 +142,17 @@ __global__ __launch_bounds__(kThreads) void proxy_kernel(ProxyArgs a) {
 // v_mfma_f64_16x16x4_f64 (gfx950 maps, cdna_hip_programming.md: A[l&15][k=l>>4], B[k=l>>4][l&15],
 // D col = l&15, row = (l>>4) + 4 reg).  One product per tile: y = dev @ P^T in T = ceil(d/16) column
 // tiles of 16, wave w owning tile w (its B fragments, all k-steps, in VGPRs for the life of the
-// block, which loops over 64-row tiles: persistent grid).  The Mahalanobis term is dev . y (the
-// same quadratic form as scipy's |dev @ U|^2, U U^T = pinv(cov) = P for the full-rank covariances
-// the proxies use; fp64 tolerance like the other summation-order differences), reduced across the
-// 16 column lanes with DPP and across the waves through LDS -- one matrix product per row instead
-// of two.  Per tile: the x tile is staged (coalesced) into LDS as dev = x - loc, each wave runs
-// S = ceil(d/4) k-steps x 4 row subtiles of MFMAs, y goes back through LDS and out as contiguous
-// grad rows.
+// block, which loops over 64-row tiles: persistent grid).  The Mahalanobis term is dev . y =
+// dev . P dev, not scipy's |dev @ U|^2: in exact arithmetic the same quadratic form (U U^T =
+// pinv(cov) = P for the full-rank covariances the proxies use), in float64 equal only up to the gap
+// between the host's two factors U U^T and P, which is NOT a summation-order difference and grows
+// with cond(cov): relative to the term about 5e-15 at cond 15, 2e-13 at cond 2e4, 7e-9 at cond 2e8
+// (tests/proxy_ref.py holds these kernels to dev . P dev within rounding and to
+// the U form within rounding plus that gap).  A second matrix product would remove it; this way it
+// is one product per row instead of two.  The row dot is every thread's quarter of a row, the
+// quarters summed with two quad DPP steps.  Per tile: the x tile is staged (coalesced) into LDS as
+// dev = x - loc, each wave runs S = ceil(d/4) k-steps x 4 row subtiles of MFMAs, y goes back
+// through LDS and out as contiguous grad rows.
 constexpr int kMfmaMaxD = 64;
 constexpr int kMfmaMaxS = kMfmaMaxD / 4;
 typedef double dbl4 __attribute__((ext_vector_type(4)));
@@ -298,7 +304,8 @@ __global__ __launch_bounds__(kThreads, 2) void proxy_mfma_kernel(ProxyArgs a) {
 //   * the output column of D row i = lk + 4r in tile c is 16c + 8(r >> 1) + 2 lk + (r & 1), i.e.
 //     exactly the input column of step s = 4c + r: each lane already holds dev at every column whose
 //     y it holds, so the Mahalanobis term dev . y is a register dot plus two cross-lane adds.
-// Summation order differs from NumPy's einsum / scipy's BLAS (fp64 tolerance, as the other kernels).
+// Summation order differs from NumPy's einsum / scipy's BLAS (fp64 rounding); dev . y against scipy's
+// |dev @ U|^2 additionally by the gap between the host's two factors, as proxy_mfma_kernel above.
 //
 // Two forms (st_tune key 7; profiles/r02_proxy_variants.log has the measured alternatives):
 //   * proxy_mfma_buf_kernel (even d, the default): every global access is a buffer instruction whose

@@ -30,7 +30,10 @@ exactly as scipy does (``_PSD``: eigh, pseudo-inverse square root; ``np.linalg.i
 constants in scipy's operation order) and the per-row work runs in one HIP kernel
 (``st_proxy_logpdf_grad``, csrc/proxy.hip).  The per-row dot products are summed in a different
 order than NumPy/BLAS: log q and grad log q agree with scipy to fp64 rounding (tests: relative
-1e-12), not bit for bit.
+1e-12), not bit for bit.  For 16 < d <= 64 the Mahalanobis term of log q is ``dev . inv(cov) dev`` where
+scipy's is ``|dev U|^2``: equal up to the gap between those two float64 factors, which is rounding-sized
+for well-scaled covariances and grows with cond(cov) (about 7e-9 of the term at cond 2e8; DESIGN.md
+section 1).
 """
 from __future__ import annotations
 

@@ -270,7 +270,11 @@ int st_greedy_step_exchange(const double *x_soa, const double *g_soa, const doub
  * scipy's _PSD(cov).U; precision (d, d) row-major = np.linalg.inv(cov); c_log = rank * log(2 pi) +
  * log_pdet (Gaussian) or A - B - C - D of scipy's multivariate_t._logpdf (t).  Writes log_q_out (n)
  * and grad_out (row-major (n, d)).  Per-row dot products are summed in a different order than
- * NumPy/BLAS (fp64 tolerance, not bit-identical).
+ * NumPy/BLAS (fp64 rounding, not bit-identical).  For 16 < d <= 64 (the matrix-core kernels) the
+ * Mahalanobis term of log_q is evaluated as dev . precision dev, not as scipy's |dev whiten|^2: the
+ * two agree up to the gap between the caller's two float64 factors (whiten whiten^T against
+ * precision), which is rounding-sized for well-scaled covariances and grows with cond(cov) -- about
+ * 7e-9 of the term at cond 2e8.  A row's outputs depend on the row alone (not on n or its position).
  * ---------------------------------------------------------------------------------------- */
 int st_proxy_logpdf_grad(const double *x, int64_t n, int32_t d, const double *loc,
                          const double *whiten, const double *precision, double df, double c_log,

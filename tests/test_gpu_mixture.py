@@ -220,3 +220,40 @@ def test_d_above_64_is_not_implemented():
                                            nat.ptr(p), None)
     with pytest.raises(NotImplementedError, match='64'):
         nat.check(rc, 'st_mixture_logpdf_score')
+
+
+def _mixture_deep_n():
+    """n at which block 0 of mixture_mfma_kernel takes four 64-row tiles and every other block three:
+    launch_mixture_mfma's grid is min(tiles, 2 x CUs)."""
+    cus = torch.cuda.get_device_properties(torch.cuda.current_device()).multi_processor_count
+    n = 64 * 3 * (2 * cus) + 21
+    tiles = (n + 63) // 64
+    grid = min(tiles, 2 * cus)
+    assert (tiles // grid, (tiles + grid - 1) // grid) == (3, 4), (cus, n, tiles, grid)
+    return n
+
+
+@pytest.mark.parametrize('zero', [None, 0, 1, 2])
+@pytest.mark.parametrize('d', [17, 64])
+def test_persistent_tile_loop_and_cross_tile_prefetch(d, zero):
+    """Every block goes three or four times round the matrix-core kernel's tile loop, so the prefetch of
+    "the next component" wraps from the last component of one tile to component 0 of the next -- with all
+    weights positive and with the first, the middle or the last component at weight 0 (the skip of an
+    a_c = -inf component hands the prefetch on).  x tiles 509 distinct rows (a prime: every lane position
+    sees every row); the first 509 outputs against the long-double restatement, every copy of a row bit for
+    bit its first copy (the header promises position independence)."""
+    n, m = _mixture_deep_n(), 509
+    base, w, means, covs = R.case(m, d, 3)
+    w = w.copy()
+    if zero is not None:
+        w[zero] = 0.0
+    idx = torch.arange(n, device='cuda') % m
+    xd = torch.from_numpy(base.copy()).cuda()[idx].contiguous()
+    log_p, score = mixture.mixture_logpdf_score(xd, w, means, covs)
+    assert log_p.shape == (n,) and score.shape == (n, d)
+    want_l, want_s = R.stable(base, w, means, covs, dtype=np.longdouble)
+    close(log_p[:m].cpu().numpy(), want_l.astype(np.float64))
+    close(score[:m].cpu().numpy(), want_s.astype(np.float64))
+    lb, sb = log_p.view(torch.int64), score.view(torch.int64)
+    assert torch.equal(lb, lb[:m][idx]), 'log_p differs between copies of a row'
+    assert torch.equal(sb, sb[:m][idx]), 'score differs between copies of a row'
