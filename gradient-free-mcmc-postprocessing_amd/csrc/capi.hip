@@ -692,6 +692,84 @@ int st_lv_log_target_density(const double* log_theta, const double* theta, int64
     return hip_check(st::launch_lv(a, false, static_cast<hipStream_t>(stream)), "lv log density launch");
 }
 
+int64_t st_lv_rwmh_workspace_bytes(int64_t chains) {
+    if (chains < 1) return -1;
+    return chains * 64;
+}
+
+int st_lv_rwmh(double* state, int64_t chains, int64_t first_chain, int64_t first_step, int64_t steps,
+               int32_t init, const double* step_size, int32_t noise_mode, uint64_t seed, double* z,
+               double* log_u, int64_t noise_ld, int64_t noise_row0, const double* t_eval, int32_t t_n,
+               const double* y_obs, const double* span_u0_tol, const double* whiten, double c_log,
+               double norm_logc, int64_t max_steps, double* samples, double* log_p, int64_t out_ld,
+               int64_t out_row0, void* stream) {
+    if (chains < 1) return fail(ST_ERR_INVALID, "chains must be >= 1 (got %lld)", (long long)chains);
+    if (steps < 1) return fail(ST_ERR_INVALID, "steps must be >= 1 (got %lld)", (long long)steps);
+    if (t_n < 1) return fail(ST_ERR_INVALID, "t_n must be >= 1");
+    if (first_step < 1) return fail(ST_ERR_INVALID, "first_step must be >= 1 (got %lld)", (long long)first_step);
+    if (first_chain < 0) return fail(ST_ERR_INVALID, "first_chain must be >= 0");
+    if (init != 0 && init != 1) return fail(ST_ERR_INVALID, "init must be 0 or 1");
+    if (noise_mode < 0 || noise_mode > 2) return fail(ST_ERR_INVALID, "noise_mode must be 0, 1 or 2");
+    if (max_steps < 1) return fail(ST_ERR_INVALID, "max_steps must be >= 1");
+    if (!state || !samples || !log_p || !t_eval || !y_obs) return fail(ST_ERR_INVALID, "NULL pointer");
+    if (!step_size || !span_u0_tol || !whiten) return fail(ST_ERR_INVALID, "NULL host settings");
+    if (noise_mode != 1) {
+        if (!z || !log_u)
+            return fail(ST_ERR_INVALID, "NULL noise arrays (z, log_u): noise_mode %d needs them", noise_mode);
+        if (noise_row0 < 0 || noise_ld < 1 || noise_row0 > noise_ld - steps)
+            return fail(ST_ERR_INVALID, "noise rows [%lld, %lld) outside the noise arrays' %lld rows",
+                        (long long)noise_row0, (long long)(noise_row0 + steps), (long long)noise_ld);
+        if (!aligned16(z) || (reinterpret_cast<uintptr_t>(log_u) & 7u))
+            return fail(ST_ERR_INVALID, "noise arrays must be aligned (z: 16 bytes, log_u: 8)");
+    }
+    if (!aligned16(state) || !aligned16(samples))
+        return fail(ST_ERR_INVALID, "state and samples must be 16-byte aligned");
+    if ((reinterpret_cast<uintptr_t>(log_p) & 7u) || (reinterpret_cast<uintptr_t>(t_eval) & 7u) ||
+        (reinterpret_cast<uintptr_t>(y_obs) & 7u))
+        return fail(ST_ERR_INVALID, "log_p, t_eval and y_obs must be 8-byte aligned");
+    if (out_ld < 1 || out_row0 < init || out_row0 > out_ld - steps)
+        return fail(ST_ERR_INVALID, "output rows [%lld, %lld) outside the output arrays' %lld rows",
+                    (long long)(out_row0 - init), (long long)(out_row0 + steps), (long long)out_ld);
+    if (init && first_step != 1) return fail(ST_ERR_INVALID, "init needs first_step = 1");
+    for (int j = 0; j < 4; ++j)
+        if (!isfinite(step_size[j]) || !(step_size[j] > 0))
+            return fail(ST_ERR_INVALID, "step size %d must be finite and > 0 (got %g)", j, step_size[j]);
+    if (!(span_u0_tol[1] > span_u0_tol[0])) return fail(ST_ERR_INVALID, "need t1 > t0 (forward integration)");
+    if (!(span_u0_tol[4] > 0) || !(span_u0_tol[5] > 0)) return fail(ST_ERR_INVALID, "rtol and atol must be > 0");
+    st::LvMcmcArgs a{};
+    a.state = state;
+    a.chains = chains;
+    a.first_chain = first_chain;
+    a.first_step = first_step;
+    a.steps = steps;
+    a.init = init;
+    for (int j = 0; j < 4; ++j) a.step[j] = step_size[j];
+    a.noise_mode = noise_mode;
+    a.seed = seed;
+    a.z = z;
+    a.log_u = log_u;
+    a.noise_ld = noise_ld;
+    a.noise_row0 = noise_row0;
+    a.t_eval = t_eval;
+    a.t_n = t_n;
+    a.y_obs = y_obs;
+    a.t0 = span_u0_tol[0];
+    a.t1 = span_u0_tol[1];
+    a.u0[0] = span_u0_tol[2];
+    a.u0[1] = span_u0_tol[3];
+    a.rtol = span_u0_tol[4];
+    a.atol = span_u0_tol[5];
+    for (int q = 0; q < 4; ++q) a.U[q] = whiten[q];
+    a.c_log = c_log;
+    a.norm_logc = norm_logc;
+    a.max_steps = max_steps;
+    a.samples = samples;
+    a.log_p = log_p;
+    a.out_ld = out_ld;
+    a.out_row0 = out_row0;
+    return hip_check(st::launch_lv_rwmh(a, static_cast<hipStream_t>(stream)), "lv rwmh launch");
+}
+
 int st_greedy_finalize(const double* cands_in, int32_t nranks, int32_t d, uint32_t* idx_out,
                        int64_t t, void* stream) {
     if (!cands_in || !idx_out) return fail(ST_ERR_INVALID, "NULL pointer");

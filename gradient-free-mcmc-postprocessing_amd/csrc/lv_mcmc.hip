@@ -1,0 +1,334 @@
+// Random-walk Metropolis sampler for the Lotka-Volterra log posterior, batched over chains: one
+// thread owns one chain and runs the Metropolis loop inside the kernel.
+//
+// Reference (Sampling.ipynb: a hand-written random-walk Metropolis-Hastings loop over
+// lotka_volterra.log_target_density, 5 chains of 500 000 rows, proposal step 0.0025; its sampler
+// package is not part of the reference tree, so the proposal x + step * N(0, I) is this project's
+// own definition).  At global step t = 1, 2, ... a chain with row x and log density lp
+//   proposes     p[j] = x[j] + step[j] * z[j]         (one multiply, one add, uncontracted: NumPy's
+//                                                       x + step * z bit for bit)
+//   evaluates    lp_new = log_target_density(p)        theta = exp(p); a theta that is zero or not
+//                                                       finite, or an integration that ends with a
+//                                                       non-zero status, rejects and counts in n_failed
+//   accepts      exactly when log_u < lp_new - lp      (strict; a NaN on either side rejects)
+//   writes       row t of the chain and log_p[t].
+// log_target_density is what lv_kernel<2> + lv_logdens_finish (lv.hip) compute -- scipy's RK45 step
+// for step (rk45_tableau.hpp, select_initial_step, the accept / reject loop, max_steps), the same
+// Horner dense output at the observation times, the same whitening by U and the same prior term --
+// with ONE difference: the sum over the observation times runs in time order in a register instead
+// of NumPy's pairwise order over a stored (t_n, n) array.  That moves the value by ~1e-13 relative,
+// inside the 1e-8 the LV tests hold to scipy.  theta = exp(p) is the device's exp (lv.hip takes
+// NumPy's from the caller): at most an ulp of theta apart, ~1e-15 relative in the density.
+// lv_rhs and rms are second copies of lv.hip's (2-state forms), kept operation for operation.
+//
+// Noise, a template parameter:
+//   supplied   z (chains, noise_ld, 4) and log_u (chains, noise_ld) written by the caller;
+//   device     NumPy's Philox (Philox4x64-10): chain c with seed s uses key (s, c); step t uses the
+//              two blocks with counter word 0 equal to 2t - 1 and 2t (the other words 0) -- the eight
+//              values np.random.Philox(key=[s, c], counter=[0, 0, 0, 0]).random_raw(8 t)[8 (t - 1):]
+//              (NumPy adds 1 to the counter before its first block).  From r0 .. r7:
+//              u_k = ((r_k >> 11) + 1) 2^-53 (k < 4), (z0, z1) = sqrt(-2 ln u0) (cos, sin)(2 pi u1),
+//              (z2, z3) likewise from u2, u3, log_u = log((r4 >> 11) 2^-53) (zero: -inf, accepts).
+//              The noise depends on (seed, chain id, t) only; RECORD also writes the z and log_u used.
+// The chain state (x, lp, accepted, n_failed: 8 words per chain) is read from a.state when the
+// launch starts and written back when it ends, so a long run is a sequence of short launches with
+// identical results.  Plain C++ and vector stores only.
+#include <hip/hip_runtime.h>
+
+#include "rk45_tableau.hpp"
+#include "stein_internal.hpp"
+
+namespace st {
+namespace {
+
+constexpr int kMcmcThreads = 64;
+
+__device__ inline void lv2_rhs(const double th[4], const double* y, double* f) {
+    const double th1 = th[0], th2 = th[1], th3 = th[2], th4 = th[3];
+    const double u1 = y[0], u2 = y[1];
+    f[0] = th1 * u1 - th2 * u1 * u2;
+    f[1] = th4 * u1 * u2 - th3 * u2;
+}
+
+// scipy common.norm: np.linalg.norm(x) / x.size ** 0.5
+__device__ inline double lv2_rms(const double* v) {
+    double s = 0.0;
+#pragma unroll
+    for (int i = 0; i < 2; ++i) s += v[i] * v[i];
+    return sqrt(s) / sqrt((double)2);
+}
+
+// log_target_density(lth), theta = exp(lth) given; NaN when the integration fails (lv_kernel<2>'s status
+// 1: step size below min_step, 2: max_steps reached).  The body follows lv_kernel<2> line for line up to the
+// per-time term, which is added to `ll` here instead of stored.  status_out carries the code itself; the
+// sampler needs only the NaN, but the form without the out-parameter compiles to a supplied-noise kernel
+// that is 8-9 % slower (A/B), so it stays.
+__device__ __forceinline__ double lv_logdens_one(const LvMcmcArgs& a, const double lth[4], const double th[4],
+                                                 int& status_out) {
+    constexpr int NS = 2;
+    const double rtol = a.rtol, atol = a.atol;
+    double y[NS], f[NS], K[rk45::kStages + 1][NS];
+    y[0] = a.u0[0];
+    y[1] = a.u0[1];
+    double t = a.t0;
+    const double t_bound = a.t1;
+    lv2_rhs(th, y, f);
+    double h_abs;
+    {
+        const double interval = fabs(t_bound - t);
+        double sc[NS], v[NS];
+#pragma unroll
+        for (int c = 0; c < NS; ++c) sc[c] = atol + fabs(y[c]) * rtol;
+#pragma unroll
+        for (int c = 0; c < NS; ++c) v[c] = y[c] / sc[c];
+        const double d0 = lv2_rms(v);
+#pragma unroll
+        for (int c = 0; c < NS; ++c) v[c] = f[c] / sc[c];
+        const double d1 = lv2_rms(v);
+        double h0 = (d0 < 1e-5 || d1 < 1e-5) ? 1e-6 : 0.01 * d0 / d1;
+        h0 = fmin(h0, interval);
+        double y1[NS], f1[NS];
+#pragma unroll
+        for (int c = 0; c < NS; ++c) y1[c] = y[c] + h0 * 1.0 * f[c];
+        lv2_rhs(th, y1, f1);
+#pragma unroll
+        for (int c = 0; c < NS; ++c) v[c] = (f1[c] - f[c]) / sc[c];
+        const double d2 = lv2_rms(v) / h0;
+        double h1;
+        if (d1 <= 1e-15 && d2 <= 1e-15) h1 = fmax(1e-6, h0 * 1e-3);
+        else h1 = pow(0.01 / fmax(d1, d2), 1.0 / (rk45::kOrder + 1));
+        h_abs = fmin(fmin(100 * h0, h1), interval);
+    }
+    int kk = 0;
+    double ll = 0.0;                  // sum of the per-time terms, in time order
+    int status = 0;
+    for (int64_t step = 0;; ++step) {
+        if (t == t_bound) break;
+        if (step >= a.max_steps) { status = 2; break; }
+        const double min_step = 10 * fabs(nextafter(t, INFINITY) - t);
+        if (h_abs < min_step) h_abs = min_step;
+        bool rejected = false;
+        double t_new, h, y_new[NS], f_new[NS];
+        for (;;) {
+            if (h_abs < min_step) { status = 1; break; }
+            h = h_abs;
+            t_new = t + h;
+            if (t_new - t_bound > 0) t_new = t_bound;
+            h = t_new - t;
+            h_abs = fabs(h);
+#pragma unroll
+            for (int c = 0; c < NS; ++c) K[0][c] = f[c];
+#pragma unroll
+            for (int s = 1; s < rk45::kStages; ++s) {
+                double ys[NS];
+#pragma unroll
+                for (int c = 0; c < NS; ++c) {
+                    double dy = K[0][c] * rk45::A[s][0];
+#pragma unroll
+                    for (int j = 1; j < s; ++j) dy += K[j][c] * rk45::A[s][j];
+                    ys[c] = y[c] + dy * h;
+                }
+                lv2_rhs(th, ys, K[s]);
+            }
+#pragma unroll
+            for (int c = 0; c < NS; ++c) {
+                double bsum = K[0][c] * rk45::B[0];
+#pragma unroll
+                for (int j = 1; j < rk45::kStages; ++j) bsum += K[j][c] * rk45::B[j];
+                y_new[c] = y[c] + h * bsum;
+            }
+            lv2_rhs(th, y_new, f_new);
+#pragma unroll
+            for (int c = 0; c < NS; ++c) K[rk45::kStages][c] = f_new[c];
+            double ev[NS];
+#pragma unroll
+            for (int c = 0; c < NS; ++c) {
+                double e = K[0][c] * rk45::E[0];
+#pragma unroll
+                for (int j = 1; j <= rk45::kStages; ++j) e += K[j][c] * rk45::E[j];
+                const double scale = atol + fmax(fabs(y[c]), fabs(y_new[c])) * rtol;
+                ev[c] = e * h / scale;
+            }
+            const double error_norm = lv2_rms(ev);
+            if (error_norm < 1) {
+                double factor = error_norm == 0 ? rk45::kMaxFactor
+                                                : fmin(rk45::kMaxFactor, rk45::kSafety * pow(error_norm, rk45::kErrorExponent));
+                if (rejected) factor = fmin(1.0, factor);
+                h_abs *= factor;
+                break;
+            }
+            h_abs *= fmax(rk45::kMinFactor, rk45::kSafety * pow(error_norm, rk45::kErrorExponent));
+            rejected = true;
+        }
+        if (status) break;
+        const double t_old = t;
+        const double hd = t_new - t_old;
+        const double inv_hd = 1.0 / hd;
+        double Q[NS][rk45::kDenseOrder];
+#pragma unroll
+        for (int c = 0; c < NS; ++c)
+#pragma unroll
+            for (int q = 0; q < rk45::kDenseOrder; ++q) {
+                double s = K[0][c] * rk45::P[0][q];
+#pragma unroll
+                for (int j = 1; j <= rk45::kStages; ++j) s += K[j][c] * rk45::P[j][q];
+                Q[c][q] = hd * s;
+            }
+        static_assert(rk45::kDenseOrder == 4, "Horner form below is written for RK45's quartic");
+        const bool last = t_new - t_bound >= 0;
+        while (kk < a.t_n && (last || a.t_eval[kk] <= t_new)) {
+            const double x = (a.t_eval[kk] - t_old) * inv_hd;
+            double u[NS];
+#pragma unroll
+            for (int c = 0; c < NS; ++c)
+                u[c] = __builtin_fma(x, __builtin_fma(x, __builtin_fma(x, __builtin_fma(x, Q[c][3], Q[c][2]), Q[c][1]),
+                                                      Q[c][0]), y[c]);
+            const double r0 = a.y_obs[2 * kk] - u[0], r1 = a.y_obs[2 * kk + 1] - u[1];
+            const double z0 = r0 * a.U[0] + r1 * a.U[2];
+            const double z1 = r0 * a.U[1] + r1 * a.U[3];
+            ll += -0.5 * (a.c_log + (z0 * z0 + z1 * z1));
+            ++kk;
+        }
+        t = t_new;
+#pragma unroll
+        for (int c = 0; c < NS; ++c) { y[c] = y_new[c]; f[c] = f_new[c]; }
+    }
+    status_out = status;
+    if (status) return NAN;
+    double lp = -0.0;                 // np.sum(norm.logpdf(log_theta)), as lv_logdens_finish
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const double x = lth[j];
+        lp += -(x * x) / 2.0 - a.norm_logc;
+    }
+    lp = 0.0 + lp;
+    return ll + lp;
+}
+
+// Philox4x64-10 (Random123; numpy/random/src/philox): one block for counter (c0, 0, 0, 0), key (k0, k1)
+__device__ inline void philox4x64_10(uint64_t c0, uint64_t k0, uint64_t k1, uint64_t out[4]) {
+    constexpr uint64_t M0 = 0xD2E7470EE14C6C93ull, M1 = 0xCA5A826395121157ull;
+    constexpr uint64_t W0 = 0x9E3779B97F4A7C15ull, W1 = 0xBB67AE8584CAA73Bull;
+    uint64_t c[4] = {c0, 0, 0, 0};
+#pragma unroll
+    for (int r = 0; r < 10; ++r) {
+        if (r) { k0 += W0; k1 += W1; }
+        const uint64_t hi0 = __umul64hi(M0, c[0]), lo0 = M0 * c[0];
+        const uint64_t hi1 = __umul64hi(M1, c[2]), lo1 = M1 * c[2];
+        const uint64_t n0 = hi1 ^ c[1] ^ k0, n2 = hi0 ^ c[3] ^ k1;
+        c[0] = n0; c[1] = lo1; c[2] = n2; c[3] = lo0;
+    }
+#pragma unroll
+    for (int q = 0; q < 4; ++q) out[q] = c[q];
+}
+
+// the noise of step t of chain `chain` (file header)
+__device__ inline void device_noise(uint64_t seed, uint64_t chain, uint64_t t, double z[4], double& log_u) {
+    uint64_t r[4], q[4];
+    philox4x64_10(2 * t - 1, seed, chain, r);
+    philox4x64_10(2 * t, seed, chain, q);
+    constexpr double k2m53 = 0x1.0p-53, kTwoPi = 6.283185307179586;
+    double u[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) u[k] = (double)((r[k] >> 11) + 1) * k2m53;
+#pragma unroll
+    for (int k = 0; k < 4; k += 2) {
+        const double rad = sqrt(-2.0 * log(u[k])), ang = kTwoPi * u[k + 1];
+        z[k] = rad * cos(ang);
+        z[k + 1] = rad * sin(ang);
+    }
+    log_u = log((double)(q[0] >> 11) * k2m53);
+}
+
+// DEVICE_NOISE: Philox noise (else a.z / a.log_u are read); RECORD (device noise only): a.z / a.log_u are
+// written.  a.init: the thread first evaluates its start row, stores it as row out_row0 - 1 and takes
+// its density as lp (NaN when that evaluation fails: every later proposal is then rejected and the
+// caller sees the NaN in log_p).
+template <bool DEVICE_NOISE, bool RECORD>
+__global__ __launch_bounds__(kMcmcThreads) void lv_rwmh_kernel(LvMcmcArgs a) {
+    const int64_t i = (int64_t)blockIdx.x * kMcmcThreads + threadIdx.x;
+    if (i >= a.chains) return;
+    double* st = a.state + 8 * i;
+    int64_t* sti = reinterpret_cast<int64_t*>(st);
+    double x[4], lp;
+    {
+        const double2 s0 = reinterpret_cast<const double2*>(st)[0], s1 = reinterpret_cast<const double2*>(st)[1];
+        x[0] = s0.x; x[1] = s0.y; x[2] = s1.x; x[3] = s1.y;
+    }
+    lp = st[4];
+    int64_t accepted = sti[5], failed = sti[6];
+    double* rows = a.samples + (i * a.out_ld + a.out_row0) * 4;
+    double* lps = a.log_p + i * a.out_ld + a.out_row0;
+    double* zs = nullptr;
+    double* lus = nullptr;
+    if (!DEVICE_NOISE || RECORD) {
+        zs = a.z + (i * a.noise_ld + a.noise_row0) * 4;
+        lus = a.log_u + i * a.noise_ld + a.noise_row0;
+    }
+    const uint64_t chain = (uint64_t)(a.first_chain + i);
+    // k = -1: the start row itself (a.init), evaluated by the same code as every proposal
+#pragma unroll 1
+    for (int64_t k = a.init ? -1 : 0; k < a.steps; ++k) {
+        const bool start = k < 0;
+        double z[4] = {0.0, 0.0, 0.0, 0.0}, log_u = 0.0;
+        if (!start) {
+            if constexpr (DEVICE_NOISE) {
+                device_noise(a.seed, chain, (uint64_t)(a.first_step + k), z, log_u);
+                if constexpr (RECORD) {
+                    reinterpret_cast<double2*>(zs + 4 * k)[0] = make_double2(z[0], z[1]);
+                    reinterpret_cast<double2*>(zs + 4 * k)[1] = make_double2(z[2], z[3]);
+                    lus[k] = log_u;
+                }
+            } else {
+                const double2 z01 = reinterpret_cast<const double2*>(zs + 4 * k)[0];
+                const double2 z23 = reinterpret_cast<const double2*>(zs + 4 * k)[1];
+                z[0] = z01.x; z[1] = z01.y; z[2] = z23.x; z[3] = z23.y;
+                log_u = lus[k];
+            }
+        }
+        double p[4], th[4];
+        bool ok = true;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            p[j] = start ? x[j] : x[j] + a.step[j] * z[j];
+            th[j] = exp(p[j]);
+            ok = ok && isfinite(th[j]) && th[j] != 0.0;
+        }
+        double lp_new = NAN;
+        if (ok) {
+            int status = 0;
+            lp_new = lv_logdens_one(a, p, th, status);
+        }
+        if (start) {
+            lp = lp_new;
+        } else {
+            if (!(lp_new == lp_new)) ++failed;      // theta out of range, or the integration failed
+            if (log_u < lp_new - lp) {
+#pragma unroll
+                for (int j = 0; j < 4; ++j) x[j] = p[j];
+                lp = lp_new;
+                ++accepted;
+            }
+        }
+        reinterpret_cast<double2*>(rows + 4 * k)[0] = make_double2(x[0], x[1]);
+        reinterpret_cast<double2*>(rows + 4 * k)[1] = make_double2(x[2], x[3]);
+        lps[k] = lp;
+    }
+    reinterpret_cast<double2*>(st)[0] = make_double2(x[0], x[1]);
+    reinterpret_cast<double2*>(st)[1] = make_double2(x[2], x[3]);
+    st[4] = lp;
+    sti[5] = accepted;
+    sti[6] = failed;
+}
+
+}  // namespace
+
+hipError_t launch_lv_rwmh(const LvMcmcArgs& a, hipStream_t s) {
+    const unsigned blocks = (unsigned)((a.chains + kMcmcThreads - 1) / kMcmcThreads);
+    if (a.noise_mode == 0) lv_rwmh_kernel<false, false><<<blocks, kMcmcThreads, 0, s>>>(a);
+    else if (a.noise_mode == 1) lv_rwmh_kernel<true, false><<<blocks, kMcmcThreads, 0, s>>>(a);
+    else lv_rwmh_kernel<true, true><<<blocks, kMcmcThreads, 0, s>>>(a);
+    return hipGetLastError();
+}
+
+}  // namespace st

@@ -191,6 +191,32 @@ struct LvArgs {
 hipError_t launch_lv(const LvArgs& a, bool gradient, hipStream_t s);
 int64_t lv_grad_workspace_bytes(int64_t n, int step_cap);
 
+// random-walk Metropolis over the LV log posterior, one chain per thread (csrc/lv_mcmc.hip)
+struct LvMcmcArgs {
+    double* state;            // (chains, 8) words: x[4], lp, accepted (int64), n_failed (int64), unused
+    int64_t chains;
+    int64_t first_chain;      // chain id of local chain 0 (Philox key word 1)
+    int64_t first_step;       // global step t of this launch's first step (>= 1)
+    int64_t steps;            // Metropolis steps in this launch
+    int init;                 // 1: evaluate the start row first, write it as row out_row0 - 1
+    double step[4];           // proposal step sizes
+    int noise_mode;           // 0 supplied, 1 device (Philox), 2 device + record into z / log_u
+    uint64_t seed;            // Philox key word 0
+    double* z;                // (chains, noise_ld, 4): read (mode 0) or written (mode 2)
+    double* log_u;            // (chains, noise_ld)
+    int64_t noise_ld, noise_row0;   // this launch's first step uses noise row noise_row0
+    const double* t_eval;     // (t_n) ascending observation times
+    int t_n;
+    const double* y_obs;      // (t_n, 2)
+    double t0, t1, u0[2], rtol, atol;
+    double U[4], c_log, norm_logc;  // as LvArgs
+    int64_t max_steps;
+    double* samples;          // (chains, out_ld, 4)
+    double* log_p;            // (chains, out_ld)
+    int64_t out_ld, out_row0; // this launch's first step writes row out_row0
+};
+hipError_t launch_lv_rwmh(const LvMcmcArgs& a, hipStream_t s);
+
 hipError_t launch_greedy_rank_exchange(const double* recs, int K, int64_t stride, int d,
                                        const MailboxPeers& peers, int rank, int nranks, int64_t t,
                                        double* recv, unsigned* status, hipStream_t s);

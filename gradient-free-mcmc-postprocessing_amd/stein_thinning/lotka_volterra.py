@@ -33,6 +33,9 @@ MEANS = np.array([0., 0.])
 C = np.diag([0.2 ** 2, 0.2 ** 2])     # observation noise covariance
 RTOL, ATOL = 1e-3, 1e-6               # scipy.integrate.solve_ivp defaults (the reference passes none)
 MAX_STEPS = 1_000_000
+# code/src/lotka_volterra.py: theta_inits (the starting points of the reference's five chains)
+THETA_INITS = np.array([[0.55, 1., 0.8, 0.8], [1.5, 1., 0.8, 0.8], [1.3, 1.33, 0.5, 0.8], [0.55, 3., 3., 0.8],
+                        [0.55, 1., 1.5, 1.5]])
 
 
 @dataclass
@@ -173,3 +176,157 @@ def for_unique(func: Callable[[np.ndarray], np.ndarray], sample: np.ndarray) -> 
     unique rows once, in one batch, and scatter back."""
     unique_samples, inverse_index = np.unique(sample, axis=0, return_inverse=True)
     return func(unique_samples)[inverse_index.reshape(-1)]
+
+
+# Metropolis steps per launch of rw_sample: a long run is a sequence of launches that hand the chain state
+# on, so that no kernel occupies the device for long.  Measured on MI355X (tools/lv_mcmc_bench.py,
+# profiles/lv_mcmc_bench.json): one launch of 256 steps takes 0.180 s at 65 536 chains (0.70 ms per step, device
+# noise), 0.170 s at 4096 and 0.140 s at 5 -- under the quarter of a second a launch is meant to stay below.
+STEPS_PER_LAUNCH = 256
+
+
+@dataclass
+class RwSample:
+    """Result of ``rw_sample`` (NumPy arrays, or ROCm tensors with ``device_out=True``)."""
+    samples: object                   # (chains, n_samples, 4) log theta; row 0 is the start
+    log_p: object                     # (chains, n_samples) log target density of every row
+    accepted: object                  # (chains,) int64: accepted proposals
+    n_failed: object                  # (chains,) int64: proposals rejected without a density (theta out of
+    #                                   range, or an RK45 integration that failed)
+    z: object = None                  # (chains, n_samples - 1, 4): the normal noise used (return_noise)
+    log_u: object = None              # (chains, n_samples - 1): the log uniforms used (return_noise)
+
+
+def _is_tensor(a) -> bool:
+    return type(a).__module__.startswith('torch')
+
+
+def rw_sample(log_theta_init, n_samples, step_size=0.0025, *, seed=None, noise=None,
+              data: Optional[LvData] = None, rtol: float = RTOL, atol: float = ATOL, max_steps: int = MAX_STEPS,
+              first_chain: int = 0, steps_per_launch: Optional[int] = None, return_noise: bool = False,
+              device_out: bool = False) -> RwSample:
+    """Random-walk Metropolis chains on the LV log posterior, one chain per GPU thread (``st_lv_rwmh``,
+    csrc/lv_mcmc.hip): the sampling stage of the reference's ``Sampling.ipynb`` (5 chains of 500 000 rows,
+    proposal step 0.0025, acceptance ~0.23), for as many chains as are given.
+
+    ``log_theta_init`` is (chains, 4) or (4,): the chains' starting rows (log theta).  Every chain gets
+    ``n_samples`` rows, row 0 being its start.  The proposal is ``x + step_size * N(0, I)`` (``step_size`` a
+    scalar or a (4,) vector) and is accepted exactly when ``log_u < log_p(proposal) - log_p(x)``.  This is the
+    project's own definition of the sampler: the reference's loop lives in a package (``toy_mcmc``) that is not
+    part of its tree.  ``log_p`` is ``log_target_density`` of every row, computed by the sampler itself (the
+    reference recomputes ``rw_log_p`` in a separate job); its sum over the observation times runs in time
+    order, ~1e-13 relative from ``log_target_density``'s pairwise order.
+
+    Noise: ``noise=(z, log_u)`` with z (chains, n_samples - 1, 4) standard normals and log_u
+    (chains, n_samples - 1) log uniforms (NumPy arrays or ROCm tensors) reproduces a host generator exactly;
+    otherwise ``seed`` (0 <= seed < 2**64) is required and chain c draws from NumPy's Philox with key
+    ``(seed, first_chain + c)``: step t uses ``np.random.Philox(key=[seed, c], counter=[0, 0, 0, 0])
+    .random_raw(8 * t)[8 * (t - 1):]`` = r0 .. r7 as u_k = ((r_k >> 11) + 1) 2^-53, (z0, z1) =
+    sqrt(-2 ln u0) (cos, sin)(2 pi u1), (z2, z3) from u2, u3, log_u = log((r4 >> 11) 2^-53).  The noise depends
+    on (seed, chain id, t) only, never on the number of chains or on ``steps_per_launch``; ``first_chain``
+    offsets the chain ids, so a run may be split over calls or devices.  ``return_noise=True`` also returns
+    the noise used.
+
+    A proposal whose theta = exp(log theta) has a zero or non-finite component, or whose integration fails,
+    is rejected and counted in ``n_failed``; a START whose own density fails raises ValueError.
+    ``device_out=True`` returns ROCm tensors (for ``thin_chains`` / ``thin_gf`` without a host round trip).
+    ``steps_per_launch`` (default ``STEPS_PER_LAUNCH``) splits the run into launches; the result does not
+    depend on it."""
+    x0 = _points(log_theta_init)
+    chains = x0.shape[0]
+    if chains < 1:
+        raise ValueError('need at least one chain')
+    if not np.all(np.isfinite(x0)):
+        raise ValueError('log_theta_init must be finite')
+    if isinstance(n_samples, bool) or int(n_samples) != n_samples or n_samples < 1:
+        raise ValueError(f'n_samples must be an integer >= 1, got {n_samples!r}')
+    n_samples = int(n_samples)
+    steps = n_samples - 1
+    step = np.asarray(step_size, dtype=np.float64)
+    if step.ndim == 0:
+        step = np.full(4, float(step))
+    if step.shape != (4,):
+        raise ValueError(f'step_size must be a scalar or (4,), got {step.shape}')
+    if not np.all(np.isfinite(step)) or np.any(step <= 0):
+        raise ValueError(f'step_size must be finite and > 0, got {step_size!r}')
+    step = np.ascontiguousarray(step)
+    if noise is None and seed is None:
+        raise ValueError('give seed= (device noise) or noise=(z, log_u)')
+    if noise is not None and seed is not None:
+        raise ValueError('give either seed= or noise=(z, log_u), not both')
+    if noise is not None:
+        if not isinstance(noise, (tuple, list)) or len(noise) != 2:
+            raise ValueError('noise must be a pair (z, log_u)')
+        z_in, lu_in = (a if _is_tensor(a) else np.asarray(a, dtype=np.float64) for a in noise)
+        if tuple(z_in.shape) != (chains, steps, 4) or tuple(lu_in.shape) != (chains, steps):
+            raise ValueError(f'noise must be z ({chains}, {steps}, 4) and log_u ({chains}, {steps}), got '
+                             f'{tuple(z_in.shape)} and {tuple(lu_in.shape)}')
+    else:
+        if isinstance(seed, bool) or int(seed) != seed or not 0 <= int(seed) < 2 ** 64:
+            raise ValueError(f'seed must be an integer in [0, 2**64), got {seed!r}')
+        seed = int(seed)
+    if isinstance(first_chain, bool) or int(first_chain) != first_chain or first_chain < 0:
+        raise ValueError(f'first_chain must be an integer >= 0, got {first_chain!r}')
+    spl = STEPS_PER_LAUNCH if steps_per_launch is None else steps_per_launch
+    if isinstance(spl, bool) or int(spl) != spl or spl < 1:
+        raise ValueError(f'steps_per_launch must be an integer >= 1, got {steps_per_launch!r}')
+    spl = int(spl)
+    if max_steps < 1:
+        raise ValueError('max_steps must be >= 1')
+
+    import torch
+    from .proxy import PsdFactor
+    data = reference_data() if data is None else data
+    t, y, s = _settings(data, rtol, atol)
+    if t.size < 1:
+        raise ValueError('need at least one observation')
+    psd = PsdFactor(np.asarray(data.cov, dtype=np.float64), allow_singular=False)
+    c_log = psd.rank * float(np.log(2 * np.pi)) + psd.log_pdet
+    U = np.ascontiguousarray(psd.U, dtype=np.float64)
+    norm_logc = float(np.log(np.sqrt(2 * np.pi)))
+    dev = nat.require_device()
+    L = nat.lib()
+    td, yd = (torch.from_numpy(a).to(dev) for a in (t, y))
+    state = torch.zeros((chains, 8), dtype=torch.float64, device=dev)   # counts: int64 zero = float 0.0 bits
+    state[:, :4] = torch.from_numpy(np.array(x0)).to(dev)          # (a copy: the caller's array may be read-only)
+    # n_samples = 1: the kernel runs at least one step; that step goes to a spare row and is dropped
+    ld = max(n_samples, 2)
+    samples = torch.empty((chains, ld, 4), dtype=torch.float64, device=dev)
+    log_p = torch.empty((chains, ld), dtype=torch.float64, device=dev)
+    mode, zd, lud = 1, None, None
+    if steps >= 1 and noise is not None:
+        mode = 0
+        zd, lud = (a.to(device=dev, dtype=torch.float64).contiguous() if _is_tensor(a)
+                   else torch.from_numpy(np.array(a, dtype=np.float64, order='C')).to(dev) for a in (z_in, lu_in))
+    elif steps >= 1 and return_noise:
+        mode = 2
+        zd = torch.empty((chains, steps, 4), dtype=torch.float64, device=dev)
+        lud = torch.empty((chains, steps), dtype=torch.float64, device=dev)
+    run = max(steps, 1)
+    for k0 in range(0, run, spl):
+        k = min(spl, run - k0)
+        nat.check(L.st_lv_rwmh(
+            nat.ptr(state), chains, int(first_chain), k0 + 1, k, 1 if k0 == 0 else 0, step.ctypes.data, mode,
+            seed if noise is None else 0, nat.ptr(zd), nat.ptr(lud), max(steps, 1), k0, nat.ptr(td), t.size,
+            nat.ptr(yd), s.ctypes.data, U.ctypes.data, c_log, norm_logc, int(max_steps), nat.ptr(samples),
+            nat.ptr(log_p), ld, k0 + 1, nat.stream_handle()), 'st_lv_rwmh')
+    bad = torch.isnan(log_p[:, 0])
+    if bool(bad.any()):
+        first = int(torch.nonzero(bad)[0, 0])
+        raise ValueError(f'rw_sample: the log target density of {int(bad.sum())} starting point(s) failed '
+                         f'(first: chain {first}): theta out of range or the RK45 integration did not finish')
+    counts = state.view(torch.int64)[:, 5:7]
+    if steps == 0:
+        counts = torch.zeros_like(counts)
+        samples, log_p = samples[:, :1], log_p[:, :1]
+        if return_noise or noise is not None:
+            zd = torch.empty((chains, 0, 4), dtype=torch.float64, device=dev)
+            lud = torch.empty((chains, 0), dtype=torch.float64, device=dev)
+    accepted, failed = counts[:, 0].clone(), counts[:, 1].clone()
+    if not return_noise:
+        zd = lud = None
+    res = RwSample(samples, log_p, accepted, failed, zd, lud)
+    if not device_out:
+        res = RwSample(*(None if a is None else a.cpu().numpy() for a in
+                         (res.samples, res.log_p, res.accepted, res.n_failed, res.z, res.log_u)))
+    return res

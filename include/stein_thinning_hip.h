@@ -396,6 +396,40 @@ int st_lv_log_target_density(const double *log_theta, const double *theta, int64
                              void *workspace, int64_t workspace_bytes, void *stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Random-walk Metropolis sampler for the LV log posterior (Sampling.ipynb's hand-written loop over
+ * lotka_volterra.log_target_density), batched over chains: one thread per chain, `steps` Metropolis
+ * steps per launch inside the kernel (csrc/lv_mcmc.hip).  At global step t = first_step + k a chain
+ * proposes p = x + step_size * z (one multiply, one add per component), evaluates
+ * lp_new = log_target_density(p) as st_lv_log_target_density does (theta = exp(p) on the device; the
+ * sum over the observation times in time order), accepts exactly when log_u < lp_new - lp, and writes
+ * row out_row0 + k of samples (chains, out_ld, 4) and log_p (chains, out_ld).  A proposal whose theta
+ * has a zero or non-finite component, or whose integration fails, is rejected and counted.
+ *   state: st_lv_rwmh_workspace_bytes(chains) = 64 chains bytes of device memory, 8 words per chain:
+ *     x[4], lp, accepted (int64), n_failed (int64), one unused; read at launch start, written at launch
+ *     end, so consecutive launches continue the chains.  init = 1 (first_step must be 1): the kernel
+ *     first evaluates lp of the state's x (lp NaN when that fails), writes the start as row
+ *     out_row0 - 1; the caller zeroes the counts.
+ *   noise_mode 0: z (chains, noise_ld, 4) and log_u (chains, noise_ld) are read, step k from row
+ *     noise_row0 + k.  1: NumPy's Philox4x64-10 on the device, key (seed, first_chain + chain), step t
+ *     from the blocks with counter word 0 = 2t - 1 and 2t, i.e. random_raw values r0 .. r7 =
+ *     np.random.Philox(key=[seed, c], counter=[0, 0, 0, 0]).random_raw(8 t)[8 (t - 1):]:
+ *     u_k = ((r_k >> 11) + 1) 2^-53, (z0, z1) = sqrt(-2 ln u0) (cos, sin)(2 pi u1), (z2, z3) from u2, u3,
+ *     log_u = log((r4 >> 11) 2^-53); z and log_u may be NULL.  2: as 1, and the noise used is written
+ *     to z / log_u.
+ *   step_size: HOST (4); span_u0_tol, whiten, c_log, norm_logc: as st_lv_log_target_density.
+ * ST_ERR_INVALID (all checked before any HIP call): NULL or misaligned pointers (state, samples, z: 16
+ * bytes; the others 8), chains < 1, steps < 1, t_n < 1, first_step < 1, first_chain < 0, a step size
+ * that is not finite or <= 0, noise_mode 0 or 2 without noise arrays, rows outside the arrays.
+ * ---------------------------------------------------------------------------------------- */
+int64_t st_lv_rwmh_workspace_bytes(int64_t chains);
+int st_lv_rwmh(double *state, int64_t chains, int64_t first_chain, int64_t first_step, int64_t steps,
+               int32_t init, const double *step_size, int32_t noise_mode, uint64_t seed, double *z,
+               double *log_u, int64_t noise_ld, int64_t noise_row0, const double *t_eval, int32_t t_n,
+               const double *y_obs, const double *span_u0_tol, const double *whiten, double c_log,
+               double norm_logc, int64_t max_steps, double *samples, double *log_p, int64_t out_ld,
+               int64_t out_row0, void *stream);
+
+/* ------------------------------------------------------------------------------------------
  * Integrand protocol -- replaces integrand(ind1, ind2) of the closures returned by
  * stein_thinning.thinning._make_stein_integrand / _make_stein_gf_integrand and
  * stein_thinning.kernel.vfk0_imq (restated at JAX_Stein_Thinning.ipynb cell 27, json ~354-361;
