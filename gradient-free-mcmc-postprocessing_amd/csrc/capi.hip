@@ -604,29 +604,42 @@ int st_mvt_moments(const double* x, int64_t n, int32_t d, const double* loc, con
 // tolerances); a point that takes more is recomputed by the single-phase kernel
 constexpr int kLvStepCap = 64;
 
-static int lv_common(st::LvArgs& a, const double* theta, int64_t n, const double* t_eval, int32_t t_n,
-                     const double* y_obs, const double* span_u0_tol, int64_t max_steps, double* out,
-                     int32_t* status) {
-    if (n < 0) return fail(ST_ERR_INVALID, "n must be >= 0");
+// the part of their arguments that every LV entry point shares, checked and stored in one place; whiten
+// may be NULL where the kernels do not read U (the gradient)
+static int lv_problem(st::LvProblem& p, const double* t_eval, int32_t t_n, const double* y_obs,
+                      const double* span_u0_tol, const double* whiten, double c_log, double norm_logc,
+                      int64_t max_steps, bool need_data) {
     if (t_n < 1) return fail(ST_ERR_INVALID, "t_n must be >= 1");
     if (!span_u0_tol) return fail(ST_ERR_INVALID, "NULL solver settings");
     if (max_steps < 1) return fail(ST_ERR_INVALID, "max_steps must be >= 1");
-    if (n > 0 && (!theta || !t_eval || !y_obs || !out || !status)) return fail(ST_ERR_INVALID, "NULL pointer");
-    const double t0 = span_u0_tol[0], t1 = span_u0_tol[1];
-    if (!(t1 > t0)) return fail(ST_ERR_INVALID, "need t1 > t0 (forward integration)");
+    if (need_data && (!t_eval || !y_obs)) return fail(ST_ERR_INVALID, "NULL pointer");
+    if (!(span_u0_tol[1] > span_u0_tol[0])) return fail(ST_ERR_INVALID, "need t1 > t0 (forward integration)");
     if (!(span_u0_tol[4] > 0) || !(span_u0_tol[5] > 0)) return fail(ST_ERR_INVALID, "rtol and atol must be > 0");
+    p.t_eval = t_eval;
+    p.t_n = t_n;
+    p.y_obs = y_obs;
+    p.t0 = span_u0_tol[0];
+    p.t1 = span_u0_tol[1];
+    p.u0[0] = span_u0_tol[2];
+    p.u0[1] = span_u0_tol[3];
+    p.rtol = span_u0_tol[4];
+    p.atol = span_u0_tol[5];
+    for (int q = 0; q < 4 && whiten; ++q) p.U[q] = whiten[q];
+    p.c_log = c_log;
+    p.norm_logc = norm_logc;
+    p.max_steps = max_steps;
+    return ST_OK;
+}
+
+static int lv_common(st::LvArgs& a, const double* theta, int64_t n, const double* t_eval, int32_t t_n,
+                     const double* y_obs, const double* span_u0_tol, const double* whiten, double c_log,
+                     double norm_logc, int64_t max_steps, double* out, int32_t* status) {
+    if (n < 0) return fail(ST_ERR_INVALID, "n must be >= 0");
+    int rc = lv_problem(a.p, t_eval, t_n, y_obs, span_u0_tol, whiten, c_log, norm_logc, max_steps, n > 0);
+    if (rc) return rc;
+    if (n > 0 && (!theta || !out || !status)) return fail(ST_ERR_INVALID, "NULL pointer");
     a.theta = theta;
     a.n = n;
-    a.t_eval = t_eval;
-    a.t_n = t_n;
-    a.y_obs = y_obs;
-    a.t0 = t0;
-    a.t1 = t1;
-    a.u0[0] = span_u0_tol[2];
-    a.u0[1] = span_u0_tol[3];
-    a.rtol = span_u0_tol[4];
-    a.atol = span_u0_tol[5];
-    a.max_steps = max_steps;
     a.out = out;
     a.status = status;
     return ST_OK;
@@ -636,7 +649,7 @@ int st_lv_grad_log_posterior(const double* theta, int64_t n, const double* t_eva
                              const double* y_obs, const double* span_u0_tol, const double* cov_inv,
                              int64_t max_steps, double* grad_out, int32_t* status, void* stream) {
     st::LvArgs a{};
-    int rc = lv_common(a, theta, n, t_eval, t_n, y_obs, span_u0_tol, max_steps, grad_out, status);
+    int rc = lv_common(a, theta, n, t_eval, t_n, y_obs, span_u0_tol, nullptr, 0.0, 0.0, max_steps, grad_out, status);
     if (rc) return rc;
     if (!cov_inv) return fail(ST_ERR_INVALID, "NULL cov_inv");
     for (int q = 0; q < 4; ++q) a.cinv[q] = cov_inv[q];
@@ -654,7 +667,7 @@ int st_lv_grad_log_posterior_ws(const double* theta, int64_t n, const double* t_
                                 int64_t max_steps, double* grad_out, int32_t* status, void* workspace,
                                 int64_t workspace_bytes, void* stream) {
     st::LvArgs a{};
-    int rc = lv_common(a, theta, n, t_eval, t_n, y_obs, span_u0_tol, max_steps, grad_out, status);
+    int rc = lv_common(a, theta, n, t_eval, t_n, y_obs, span_u0_tol, nullptr, 0.0, 0.0, max_steps, grad_out, status);
     if (rc) return rc;
     if (!cov_inv) return fail(ST_ERR_INVALID, "NULL cov_inv");
     if (n > 0 && !workspace) return fail(ST_ERR_INVALID, "NULL workspace");
@@ -678,15 +691,12 @@ int st_lv_log_target_density(const double* log_theta, const double* theta, int64
                              double norm_logc, int64_t max_steps, double* out, int32_t* status,
                              void* workspace, int64_t workspace_bytes, void* stream) {
     st::LvArgs a{};
-    int rc = lv_common(a, theta, n, t_eval, t_n, y_obs, span_u0_tol, max_steps, out, status);
+    int rc = lv_common(a, theta, n, t_eval, t_n, y_obs, span_u0_tol, whiten, c_log, norm_logc, max_steps, out, status);
     if (rc) return rc;
     if (!whiten) return fail(ST_ERR_INVALID, "NULL whiten");
     if (n > 0 && (!log_theta || !workspace)) return fail(ST_ERR_INVALID, "NULL log_theta / workspace");
     if (workspace_bytes < n * (int64_t)t_n * 8) return fail(ST_ERR_INVALID, "workspace too small");
-    for (int q = 0; q < 4; ++q) a.U[q] = whiten[q];
     a.log_theta = log_theta;
-    a.c_log = c_log;
-    a.norm_logc = norm_logc;
     a.work = static_cast<double*>(workspace);
     if (n == 0) return ST_OK;
     return hip_check(st::launch_lv(a, false, static_cast<hipStream_t>(stream)), "lv log density launch");
@@ -705,14 +715,15 @@ int st_lv_rwmh(double* state, int64_t chains, int64_t first_chain, int64_t first
                int64_t out_row0, void* stream) {
     if (chains < 1) return fail(ST_ERR_INVALID, "chains must be >= 1 (got %lld)", (long long)chains);
     if (steps < 1) return fail(ST_ERR_INVALID, "steps must be >= 1 (got %lld)", (long long)steps);
-    if (t_n < 1) return fail(ST_ERR_INVALID, "t_n must be >= 1");
+    st::LvMcmcArgs a{};
+    int rc = lv_problem(a.p, t_eval, t_n, y_obs, span_u0_tol, whiten, c_log, norm_logc, max_steps, true);
+    if (rc) return rc;
     if (first_step < 1) return fail(ST_ERR_INVALID, "first_step must be >= 1 (got %lld)", (long long)first_step);
     if (first_chain < 0) return fail(ST_ERR_INVALID, "first_chain must be >= 0");
     if (init != 0 && init != 1) return fail(ST_ERR_INVALID, "init must be 0 or 1");
     if (noise_mode < 0 || noise_mode > 2) return fail(ST_ERR_INVALID, "noise_mode must be 0, 1 or 2");
-    if (max_steps < 1) return fail(ST_ERR_INVALID, "max_steps must be >= 1");
-    if (!state || !samples || !log_p || !t_eval || !y_obs) return fail(ST_ERR_INVALID, "NULL pointer");
-    if (!step_size || !span_u0_tol || !whiten) return fail(ST_ERR_INVALID, "NULL host settings");
+    if (!state || !samples || !log_p) return fail(ST_ERR_INVALID, "NULL pointer");
+    if (!step_size || !whiten) return fail(ST_ERR_INVALID, "NULL host settings");
     if (noise_mode != 1) {
         if (!z || !log_u)
             return fail(ST_ERR_INVALID, "NULL noise arrays (z, log_u): noise_mode %d needs them", noise_mode);
@@ -734,9 +745,6 @@ int st_lv_rwmh(double* state, int64_t chains, int64_t first_chain, int64_t first
     for (int j = 0; j < 4; ++j)
         if (!isfinite(step_size[j]) || !(step_size[j] > 0))
             return fail(ST_ERR_INVALID, "step size %d must be finite and > 0 (got %g)", j, step_size[j]);
-    if (!(span_u0_tol[1] > span_u0_tol[0])) return fail(ST_ERR_INVALID, "need t1 > t0 (forward integration)");
-    if (!(span_u0_tol[4] > 0) || !(span_u0_tol[5] > 0)) return fail(ST_ERR_INVALID, "rtol and atol must be > 0");
-    st::LvMcmcArgs a{};
     a.state = state;
     a.chains = chains;
     a.first_chain = first_chain;
@@ -750,19 +758,6 @@ int st_lv_rwmh(double* state, int64_t chains, int64_t first_chain, int64_t first
     a.log_u = log_u;
     a.noise_ld = noise_ld;
     a.noise_row0 = noise_row0;
-    a.t_eval = t_eval;
-    a.t_n = t_n;
-    a.y_obs = y_obs;
-    a.t0 = span_u0_tol[0];
-    a.t1 = span_u0_tol[1];
-    a.u0[0] = span_u0_tol[2];
-    a.u0[1] = span_u0_tol[3];
-    a.rtol = span_u0_tol[4];
-    a.atol = span_u0_tol[5];
-    for (int q = 0; q < 4; ++q) a.U[q] = whiten[q];
-    a.c_log = c_log;
-    a.norm_logc = norm_logc;
-    a.max_steps = max_steps;
     a.samples = samples;
     a.log_p = log_p;
     a.out_ld = out_ld;

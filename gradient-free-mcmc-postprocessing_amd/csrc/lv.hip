@@ -7,19 +7,15 @@
 //     dense_output=True).sol(t): RK45 (Dormand-Prince), rtol 1e-3, atol 1e-6 (scipy defaults)
 //   log_target_density(log_theta) = sum_k mvn.logpdf(y_k - u(t_k), 0, C) + sum_j norm.logpdf(log_theta_j)
 //     u from solve_ivp(lotka_volterra, ...) (the 2-state system: its own step sequence)
-// One thread integrates one parameter point with scipy's algorithm step for step: initial step
-// selection (common.select_initial_step), the accept / reject loop of RungeKutta._step_impl
-// (SAFETY 0.9, factors in [0.2, 10], error exponent -1/5, RMS error norm), the tableau as scipy
-// holds it (rk45_tableau.hpp, generated), and dense output y = h Q p(x) + y_old per accepted step
-// with OdeSolution's segment rule (t in (t_j, t_j+1] -> segment j).  The observation points are
-// consumed in time order while the integration proceeds, so no trajectory is stored; the gradient
-// sums over time points sequentially (np.sum(axis=0) of the (t_n, 4) terms).  Summation orders
-// inside the BLAS products scipy uses (np.dot of stages) are not reproducible bit for bit:
-// results agree with scipy to rounding as long as the step sequences coincide.
+// One thread integrates one parameter point with scipy's algorithm step for step (lv_rk45.hpp, shared
+// with the sampler of lv_mcmc.hip: the integrator, its dense output and the density's terms).  The
+// observation points are consumed in time order while the integration proceeds, so no trajectory is
+// stored; the gradient sums over time points sequentially (np.sum(axis=0) of the (t_n, 4) terms).
+// Summation orders inside the BLAS products scipy uses (np.dot of stages) are not reproducible bit
+// for bit: results agree with scipy to rounding as long as the step sequences coincide.
 #include <hip/hip_runtime.h>
 
-#include "rk45_tableau.hpp"
-#include "stein_internal.hpp"
+#include "lv_rk45.hpp"
 
 namespace st {
 namespace {
@@ -27,35 +23,6 @@ namespace {
 constexpr int kLvThreads = 64;
 constexpr int kLvOverflow = 3;     // status: more accepted steps than the step table holds (internal)
 constexpr int kLvStepRec = 56;     // doubles per recorded step: t_old, 1/h, k_begin, k_end, y[10], hQ[10][4], pad
-
-template <int NS>
-__device__ inline void lv_rhs(const double th[4], const double* y, double* f) {
-    const double th1 = th[0], th2 = th[1], th3 = th[2], th4 = th[3];
-    const double u1 = y[0], u2 = y[1];
-    f[0] = th1 * u1 - th2 * u1 * u2;
-    f[1] = th4 * u1 * u2 - th3 * u2;
-    if constexpr (NS == 10) {
-        const double w1 = y[2], w2 = y[3], w3 = y[4], w4 = y[5];
-        const double w5 = y[6], w6 = y[7], w7 = y[8], w8 = y[9];
-        f[2] = u1 + (th1 - th2 * u2) * w1 - th2 * u1 * w5;
-        f[3] = -u1 * u2 + (th1 - th2 * u2) * w2 - th2 * u1 * w6;
-        f[4] = (th1 - th2 * u2) * w3 - th2 * u1 * w7;
-        f[5] = (th1 - th2 * u2) * w4 - th2 * u1 * w8;
-        f[6] = th4 * u2 * w1 + (th4 * u1 - th3) * w5;
-        f[7] = th4 * u2 * w2 + (th4 * u1 - th3) * w6;
-        f[8] = -u2 + th4 * u2 * w3 + (th4 * u1 - th3) * w7;
-        f[9] = u1 * u2 + th4 * u2 * w4 + (th4 * u1 - th3) * w8;
-    }
-}
-
-// scipy common.norm: np.linalg.norm(x) / x.size ** 0.5
-template <int NS>
-__device__ inline double rms(const double* v) {
-    double s = 0.0;
-#pragma unroll
-    for (int i = 0; i < NS; ++i) s += v[i] * v[i];
-    return sqrt(s) / sqrt((double)NS);
-}
 
 // NS = 10: gradient of the log posterior -> out[4 i + j]; NS = 2: per-time log-likelihood terms ->
 // work[k n + i] (summed by lv_logdens_finish).
@@ -74,138 +41,24 @@ __global__ __launch_bounds__(kLvThreads) void lv_kernel(LvArgs a) {
     double th[4];
 #pragma unroll
     for (int j = 0; j < 4; ++j) th[j] = a.theta[4 * i + j];
-    const double rtol = a.rtol, atol = a.atol;
-    double y[NS], f[NS], K[rk45::kStages + 1][NS];
-#pragma unroll
-    for (int c = 0; c < NS; ++c) y[c] = c < 2 ? a.u0[c] : 0.0;
-    double t = a.t0;
-    const double t_bound = a.t1;
-    lv_rhs<NS>(th, y, f);
-    // ---- select_initial_step (order = error estimator order 4, max_step = inf, direction +1)
-    double h_abs;
-    {
-        const double interval = fabs(t_bound - t);
-        double sc[NS], v[NS];
-#pragma unroll
-        for (int c = 0; c < NS; ++c) sc[c] = atol + fabs(y[c]) * rtol;
-#pragma unroll
-        for (int c = 0; c < NS; ++c) v[c] = y[c] / sc[c];
-        const double d0 = rms<NS>(v);
-#pragma unroll
-        for (int c = 0; c < NS; ++c) v[c] = f[c] / sc[c];
-        const double d1 = rms<NS>(v);
-        double h0 = (d0 < 1e-5 || d1 < 1e-5) ? 1e-6 : 0.01 * d0 / d1;
-        h0 = fmin(h0, interval);
-        double y1[NS], f1[NS];
-#pragma unroll
-        for (int c = 0; c < NS; ++c) y1[c] = y[c] + h0 * 1.0 * f[c];
-        lv_rhs<NS>(th, y1, f1);
-#pragma unroll
-        for (int c = 0; c < NS; ++c) v[c] = (f1[c] - f[c]) / sc[c];
-        const double d2 = rms<NS>(v) / h0;
-        double h1;
-        if (d1 <= 1e-15 && d2 <= 1e-15) h1 = fmax(1e-6, h0 * 1e-3);
-        else h1 = pow(0.01 / fmax(d1, d2), 1.0 / (rk45::kOrder + 1));
-        h_abs = fmin(fmin(100 * h0, h1), interval);   // max_step = inf
-    }
     int kk = 0;                       // next observation point
     int nrec = 0;                     // RECORD: accepted steps stored
     double acc[4] = {0.0, 0.0, 0.0, 0.0};
-    int32_t status = 0;
-    for (int64_t step = 0;; ++step) {
-        if (t == t_bound) break;      // OdeSolver.step: finished
-        if (step >= a.max_steps) { status = 2; break; }
-        const double min_step = 10 * fabs(nextafter(t, INFINITY) - t);
-        if (h_abs < min_step) h_abs = min_step;   // (h_abs > max_step = inf never)
-        bool rejected = false;
-        double t_new, h, y_new[NS], f_new[NS];
-        for (;;) {
-            if (h_abs < min_step) { status = 1; break; }
-            h = h_abs;
-            t_new = t + h;
-            if (t_new - t_bound > 0) t_new = t_bound;
-            h = t_new - t;
-            h_abs = fabs(h);
-            // rk_step
-#pragma unroll
-            for (int c = 0; c < NS; ++c) K[0][c] = f[c];
-#pragma unroll
-            for (int s = 1; s < rk45::kStages; ++s) {
-                double ys[NS];
-#pragma unroll
-                for (int c = 0; c < NS; ++c) {
-                    double dy = K[0][c] * rk45::A[s][0];
-#pragma unroll
-                    for (int j = 1; j < s; ++j) dy += K[j][c] * rk45::A[s][j];
-                    ys[c] = y[c] + dy * h;
-                }
-                lv_rhs<NS>(th, ys, K[s]);
-            }
-#pragma unroll
-            for (int c = 0; c < NS; ++c) {
-                double bsum = K[0][c] * rk45::B[0];
-#pragma unroll
-                for (int j = 1; j < rk45::kStages; ++j) bsum += K[j][c] * rk45::B[j];
-                y_new[c] = y[c] + h * bsum;
-            }
-            lv_rhs<NS>(th, y_new, f_new);
-#pragma unroll
-            for (int c = 0; c < NS; ++c) K[rk45::kStages][c] = f_new[c];
-            double ev[NS];
-#pragma unroll
-            for (int c = 0; c < NS; ++c) {
-                double e = K[0][c] * rk45::E[0];
-#pragma unroll
-                for (int j = 1; j <= rk45::kStages; ++j) e += K[j][c] * rk45::E[j];
-                const double scale = atol + fmax(fabs(y[c]), fabs(y_new[c])) * rtol;
-                ev[c] = e * h / scale;
-            }
-            const double error_norm = rms<NS>(ev);
-            if (error_norm < 1) {
-                double factor = error_norm == 0 ? rk45::kMaxFactor
-                                                : fmin(rk45::kMaxFactor, rk45::kSafety * pow(error_norm, rk45::kErrorExponent));
-                if (rejected) factor = fmin(1.0, factor);
-                h_abs *= factor;
-                break;
-            }
-            h_abs *= fmax(rk45::kMinFactor, rk45::kSafety * pow(error_norm, rk45::kErrorExponent));
-            rejected = true;
-        }
-        if (status) break;
-        // dense output of this step: Q = K^T P; points t in (t_old, t_new] (all remaining at the end).
-        // scipy evaluates h Q p(x) + y_old with p = (x, x^2, x^3, x^4); here hQ is formed once per
-        // step and p is applied in Horner form, x = (t - t_old) * (1 / h): the dense output feeds
-        // nothing back into the step sequence, so these roundings only move the result within the
-        // 1e-8 tolerance of the BLAS-ordered reference (tests/test_gpu_lv.py), at ~45 instead of
-        // ~110 fp64 instructions per observation point
-        const double t_old = t;
-        const double hd = t_new - t_old;
-        const double inv_hd = 1.0 / hd;
-        double Q[NS][rk45::kDenseOrder];
-#pragma unroll
-        for (int c = 0; c < NS; ++c)
-#pragma unroll
-            for (int q = 0; q < rk45::kDenseOrder; ++q) {
-                double s = K[0][c] * rk45::P[0][q];
-#pragma unroll
-                for (int j = 1; j <= rk45::kStages; ++j) s += K[j][c] * rk45::P[j][q];
-                Q[c][q] = hd * s;
-            }
-        static_assert(rk45::kDenseOrder == 4, "Horner form below is written for RK45's quartic");
-        const bool last = t_new - t_bound >= 0;
+    const int32_t status = lv_integrate<NS>(th, a.p, [&](double t_old, double t_new, double inv_hd, const double* y,
+                                                         const double (*Q)[rk45::kDenseOrder], bool last) {
         if constexpr (RECORD) {
             // observation range of this step: (t_old, t_new], everything left at the last step
-            int k_end = a.t_n;
+            int k_end = a.p.t_n;
             if (!last) {
-                int lo = kk, hi = a.t_n;   // first index with t_eval > t_new
+                int lo = kk, hi = a.p.t_n;   // first index with t_eval > t_new
                 while (lo < hi) {
                     const int mid = (lo + hi) >> 1;
-                    if (a.t_eval[mid] <= t_new) lo = mid + 1; else hi = mid;
+                    if (a.p.t_eval[mid] <= t_new) lo = mid + 1; else hi = mid;
                 }
                 k_end = lo;
             }
             if (k_end > kk) {
-                if (nrec >= a.step_cap) { status = kLvOverflow; break; }
+                if (nrec >= a.step_cap) return kLvOverflow;
                 double* r = a.steps + ((int64_t)i * a.step_cap + nrec) * kLvStepRec;
                 r[0] = t_old;
                 r[1] = inv_hd;
@@ -220,31 +73,21 @@ __global__ __launch_bounds__(kLvThreads) void lv_kernel(LvArgs a) {
                 ++nrec;
                 kk = k_end;
             }
+        } else {
+            lv_observe<NS>(a.p, kk, t_old, t_new, inv_hd, y, Q, last, [&](int k, const double* u) {
+                if constexpr (NS == 10) {
+                    const double r0 = a.p.y_obs[2 * k] - u[0], r1 = a.p.y_obs[2 * k + 1] - u[1];
+                    const double g0 = a.cinv[0] * r0 + a.cinv[1] * r1;
+                    const double g1 = a.cinv[2] * r0 + a.cinv[3] * r1;
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) acc[j] += u[2 + j] * g0 + u[6 + j] * g1;
+                } else {
+                    a.work[(int64_t)k * a.n + i] = lv_loglik_term(a.p, k, u);
+                }
+            });
         }
-        while (!RECORD && kk < a.t_n && (last || a.t_eval[kk] <= t_new)) {
-            const double x = (a.t_eval[kk] - t_old) * inv_hd;
-            double u[NS];
-#pragma unroll
-            for (int c = 0; c < NS; ++c)
-                u[c] = __builtin_fma(x, __builtin_fma(x, __builtin_fma(x, __builtin_fma(x, Q[c][3], Q[c][2]), Q[c][1]),
-                                                      Q[c][0]), y[c]);
-            const double r0 = a.y_obs[2 * kk] - u[0], r1 = a.y_obs[2 * kk + 1] - u[1];
-            if constexpr (NS == 10) {
-                const double g0 = a.cinv[0] * r0 + a.cinv[1] * r1;
-                const double g1 = a.cinv[2] * r0 + a.cinv[3] * r1;
-#pragma unroll
-                for (int j = 0; j < 4; ++j) acc[j] += u[2 + j] * g0 + u[6 + j] * g1;
-            } else {
-                const double z0 = r0 * a.U[0] + r1 * a.U[2];
-                const double z1 = r0 * a.U[1] + r1 * a.U[3];
-                a.work[(int64_t)kk * a.n + i] = -0.5 * (a.c_log + (z0 * z0 + z1 * z1));
-            }
-            ++kk;
-        }
-        t = t_new;
-#pragma unroll
-        for (int c = 0; c < NS; ++c) { y[c] = y_new[c]; f[c] = f_new[c]; }
-    }
+        return 0;
+    });
     a.status[i] = status;
     if constexpr (RECORD) {
         a.nsteps[i] = nrec;
@@ -260,7 +103,7 @@ __global__ __launch_bounds__(kLvThreads) void lv_kernel(LvArgs a) {
         for (int j = 0; j < 4; ++j)
             a.out[4 * i + j] = status ? NAN : acc[j] - log(th[j]) / th[j];
     } else if (status) {
-        for (; kk < a.t_n; ++kk) a.work[(int64_t)kk * a.n + i] = NAN;
+        for (; kk < a.p.t_n; ++kk) a.work[(int64_t)kk * a.n + i] = NAN;
     }
 }
 
@@ -321,15 +164,8 @@ __device__ double pairwise_sum_strided(const double* a, int64_t n, int64_t strid
 __global__ __launch_bounds__(kLvThreads) void lv_logdens_finish(LvArgs a) {
     const int64_t i = (int64_t)blockIdx.x * kLvThreads + threadIdx.x;
     if (i >= a.n) return;
-    const double ll = 0.0 + pairwise_sum_strided(a.work + i, a.t_n, a.n);
-    double lp = -0.0;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        const double x = a.log_theta[4 * i + j];
-        lp += -(x * x) / 2.0 - a.norm_logc;
-    }
-    lp = 0.0 + lp;
-    a.out[i] = ll + lp;
+    const double ll = 0.0 + pairwise_sum_strided(a.work + i, a.p.t_n, a.n);
+    a.out[i] = ll + lv_log_prior(a.log_theta + 4 * i, a.p.norm_logc);
 }
 
 __device__ __forceinline__ int wave_sum_int(int v) {
@@ -358,10 +194,10 @@ __global__ __launch_bounds__(64 * WPB) void lv_dense_kernel(LvArgs a) {
     __shared__ int pstart_sh[WPB][65];
     extern __shared__ double obs_sh[];      // LDS: t[t_n], y0[t_n], y1[t_n]
     if constexpr (LDS) {
-        for (int e = threadIdx.x; e < a.t_n; e += 64 * WPB) {
-            obs_sh[e] = a.t_eval[e];
-            obs_sh[a.t_n + e] = a.y_obs[2 * e];
-            obs_sh[2 * a.t_n + e] = a.y_obs[2 * e + 1];
+        for (int e = threadIdx.x; e < a.p.t_n; e += 64 * WPB) {
+            obs_sh[e] = a.p.t_eval[e];
+            obs_sh[a.p.t_n + e] = a.p.y_obs[2 * e];
+            obs_sh[2 * a.p.t_n + e] = a.p.y_obs[2 * e + 1];
         }
         __syncthreads();
     }
@@ -378,7 +214,7 @@ __global__ __launch_bounds__(64 * WPB) void lv_dense_kernel(LvArgs a) {
     }
     // smallest P with sum_s ceil(len_s / P) <= 64 KP (ns <= 64 guarantees P = max len qualifies)
     constexpr int kPieces = 64 * KP;
-    int plo = (a.t_n + kPieces - 1) / kPieces, phi = len;
+    int plo = (a.p.t_n + kPieces - 1) / kPieces, phi = len;
 #pragma unroll
     for (int off = 32; off >= 1; off >>= 1) phi = max(phi, __shfl_xor(phi, off));
     if (plo > phi) plo = phi;
@@ -442,21 +278,18 @@ __global__ __launch_bounds__(64 * WPB) void lv_dense_kernel(LvArgs a) {
             const int kc = k < ke ? k : ke - 1;    // past the piece: a harmless reload, unused
             if constexpr (LDS) {
                 tk = obs_sh[kc];
-                o0 = obs_sh[a.t_n + kc];
-                o1 = obs_sh[2 * a.t_n + kc];
+                o0 = obs_sh[a.p.t_n + kc];
+                o1 = obs_sh[2 * a.p.t_n + kc];
             } else {
-                tk = a.t_eval[kc];
-                o0 = a.y_obs[2 * kc];
-                o1 = a.y_obs[2 * kc + 1];
+                tk = a.p.t_eval[kc];
+                o0 = a.p.y_obs[2 * kc];
+                o1 = a.p.y_obs[2 * kc + 1];
             }
         };
         auto point = [&](double tk, double o0, double o1) {
             const double x = (tk - t_old) * inv_hd;
             double u[10];
-#pragma unroll
-            for (int c = 0; c < 10; ++c)
-                u[c] = __builtin_fma(x, __builtin_fma(x, __builtin_fma(x, __builtin_fma(x, Q[c][3], Q[c][2]),
-                                                                       Q[c][1]), Q[c][0]), y[c]);
+            lv_horner<10>(x, y, Q, u);
             const double r0 = o0 - u[0], r1 = o1 - u[1];
             const double g0 = c0 * r0 + c1 * r1;
             const double g1 = c2 * r0 + c3 * r1;
@@ -526,7 +359,7 @@ hipError_t launch_lv(const LvArgs& a, bool gradient, hipStream_t s) {
         if (e != hipSuccess) return e;
         // observations in LDS when they fit next to the kernel's static LDS (pstart_sh: 8 x 65 ints) in
         // the default 64 KB per block (t_n <= 2643; ADVICE r04: the static part counts too)
-        const size_t obs_bytes = (size_t)a.t_n * 3 * sizeof(double);
+        const size_t obs_bytes = (size_t)a.p.t_n * 3 * sizeof(double);
         const int kp = g_lv_pieces > 0 ? g_lv_pieces : 1;
         if (obs_bytes + sizeof(int) * 8 * 65 <= 65536 && g_lv_global_obs != 1) {
             const unsigned nb = (unsigned)((a.n + 7) / 8);

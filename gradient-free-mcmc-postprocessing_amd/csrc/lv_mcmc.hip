@@ -12,14 +12,12 @@
 //                                                       non-zero status, rejects and counts in n_failed
 //   accepts      exactly when log_u < lp_new - lp      (strict; a NaN on either side rejects)
 //   writes       row t of the chain and log_p[t].
-// log_target_density is what lv_kernel<2> + lv_logdens_finish (lv.hip) compute -- scipy's RK45 step
-// for step (rk45_tableau.hpp, select_initial_step, the accept / reject loop, max_steps), the same
-// Horner dense output at the observation times, the same whitening by U and the same prior term --
-// with ONE difference: the sum over the observation times runs in time order in a register instead
-// of NumPy's pairwise order over a stored (t_n, n) array.  That moves the value by ~1e-13 relative,
-// inside the 1e-8 the LV tests hold to scipy.  theta = exp(p) is the device's exp (lv.hip takes
+// log_target_density is what lv_kernel<2> + lv_logdens_finish (lv.hip) compute, through the same code
+// (lv_rk45.hpp: the integrator, the dense output at the observation times, the whitening by U and the
+// prior term), with ONE difference: the sum over the observation times runs in time order in a register
+// instead of NumPy's pairwise order over a stored (t_n, n) array.  That moves the value by ~1e-13
+// relative, inside the 1e-8 the LV tests hold to scipy.  theta = exp(p) is the device's exp (lv.hip takes
 // NumPy's from the caller): at most an ulp of theta apart, ~1e-15 relative in the density.
-// lv_rhs and rms are second copies of lv.hip's (2-state forms), kept operation for operation.
 //
 // Noise, a template parameter:
 //   supplied   z (chains, noise_ld, 4) and log_u (chains, noise_ld) written by the caller;
@@ -35,174 +33,27 @@
 // identical results.  Plain C++ and vector stores only.
 #include <hip/hip_runtime.h>
 
-#include "rk45_tableau.hpp"
-#include "stein_internal.hpp"
+#include "lv_rk45.hpp"
 
 namespace st {
 namespace {
 
 constexpr int kMcmcThreads = 64;
 
-__device__ inline void lv2_rhs(const double th[4], const double* y, double* f) {
-    const double th1 = th[0], th2 = th[1], th3 = th[2], th4 = th[3];
-    const double u1 = y[0], u2 = y[1];
-    f[0] = th1 * u1 - th2 * u1 * u2;
-    f[1] = th4 * u1 * u2 - th3 * u2;
-}
-
-// scipy common.norm: np.linalg.norm(x) / x.size ** 0.5
-__device__ inline double lv2_rms(const double* v) {
-    double s = 0.0;
-#pragma unroll
-    for (int i = 0; i < 2; ++i) s += v[i] * v[i];
-    return sqrt(s) / sqrt((double)2);
-}
-
-// log_target_density(lth), theta = exp(lth) given; NaN when the integration fails (lv_kernel<2>'s status
-// 1: step size below min_step, 2: max_steps reached).  The body follows lv_kernel<2> line for line up to the
-// per-time term, which is added to `ll` here instead of stored.  status_out carries the code itself; the
-// sampler needs only the NaN, but the form without the out-parameter compiles to a supplied-noise kernel
-// that is 8-9 % slower (A/B), so it stays.
-__device__ __forceinline__ double lv_logdens_one(const LvMcmcArgs& a, const double lth[4], const double th[4],
-                                                 int& status_out) {
-    constexpr int NS = 2;
-    const double rtol = a.rtol, atol = a.atol;
-    double y[NS], f[NS], K[rk45::kStages + 1][NS];
-    y[0] = a.u0[0];
-    y[1] = a.u0[1];
-    double t = a.t0;
-    const double t_bound = a.t1;
-    lv2_rhs(th, y, f);
-    double h_abs;
-    {
-        const double interval = fabs(t_bound - t);
-        double sc[NS], v[NS];
-#pragma unroll
-        for (int c = 0; c < NS; ++c) sc[c] = atol + fabs(y[c]) * rtol;
-#pragma unroll
-        for (int c = 0; c < NS; ++c) v[c] = y[c] / sc[c];
-        const double d0 = lv2_rms(v);
-#pragma unroll
-        for (int c = 0; c < NS; ++c) v[c] = f[c] / sc[c];
-        const double d1 = lv2_rms(v);
-        double h0 = (d0 < 1e-5 || d1 < 1e-5) ? 1e-6 : 0.01 * d0 / d1;
-        h0 = fmin(h0, interval);
-        double y1[NS], f1[NS];
-#pragma unroll
-        for (int c = 0; c < NS; ++c) y1[c] = y[c] + h0 * 1.0 * f[c];
-        lv2_rhs(th, y1, f1);
-#pragma unroll
-        for (int c = 0; c < NS; ++c) v[c] = (f1[c] - f[c]) / sc[c];
-        const double d2 = lv2_rms(v) / h0;
-        double h1;
-        if (d1 <= 1e-15 && d2 <= 1e-15) h1 = fmax(1e-6, h0 * 1e-3);
-        else h1 = pow(0.01 / fmax(d1, d2), 1.0 / (rk45::kOrder + 1));
-        h_abs = fmin(fmin(100 * h0, h1), interval);
-    }
+// log_target_density(lth), theta = exp(lth) given; NaN when the integration fails (lv_integrate's status 1:
+// step size below min_step, 2: max_steps reached).  lv_kernel<2>'s integration and per-time term, the term
+// added to `ll` in time order instead of stored.
+__device__ __forceinline__ double lv_logdens_one(const LvProblem& p, const double lth[4], const double th[4]) {
     int kk = 0;
     double ll = 0.0;                  // sum of the per-time terms, in time order
-    int status = 0;
-    for (int64_t step = 0;; ++step) {
-        if (t == t_bound) break;
-        if (step >= a.max_steps) { status = 2; break; }
-        const double min_step = 10 * fabs(nextafter(t, INFINITY) - t);
-        if (h_abs < min_step) h_abs = min_step;
-        bool rejected = false;
-        double t_new, h, y_new[NS], f_new[NS];
-        for (;;) {
-            if (h_abs < min_step) { status = 1; break; }
-            h = h_abs;
-            t_new = t + h;
-            if (t_new - t_bound > 0) t_new = t_bound;
-            h = t_new - t;
-            h_abs = fabs(h);
-#pragma unroll
-            for (int c = 0; c < NS; ++c) K[0][c] = f[c];
-#pragma unroll
-            for (int s = 1; s < rk45::kStages; ++s) {
-                double ys[NS];
-#pragma unroll
-                for (int c = 0; c < NS; ++c) {
-                    double dy = K[0][c] * rk45::A[s][0];
-#pragma unroll
-                    for (int j = 1; j < s; ++j) dy += K[j][c] * rk45::A[s][j];
-                    ys[c] = y[c] + dy * h;
-                }
-                lv2_rhs(th, ys, K[s]);
-            }
-#pragma unroll
-            for (int c = 0; c < NS; ++c) {
-                double bsum = K[0][c] * rk45::B[0];
-#pragma unroll
-                for (int j = 1; j < rk45::kStages; ++j) bsum += K[j][c] * rk45::B[j];
-                y_new[c] = y[c] + h * bsum;
-            }
-            lv2_rhs(th, y_new, f_new);
-#pragma unroll
-            for (int c = 0; c < NS; ++c) K[rk45::kStages][c] = f_new[c];
-            double ev[NS];
-#pragma unroll
-            for (int c = 0; c < NS; ++c) {
-                double e = K[0][c] * rk45::E[0];
-#pragma unroll
-                for (int j = 1; j <= rk45::kStages; ++j) e += K[j][c] * rk45::E[j];
-                const double scale = atol + fmax(fabs(y[c]), fabs(y_new[c])) * rtol;
-                ev[c] = e * h / scale;
-            }
-            const double error_norm = lv2_rms(ev);
-            if (error_norm < 1) {
-                double factor = error_norm == 0 ? rk45::kMaxFactor
-                                                : fmin(rk45::kMaxFactor, rk45::kSafety * pow(error_norm, rk45::kErrorExponent));
-                if (rejected) factor = fmin(1.0, factor);
-                h_abs *= factor;
-                break;
-            }
-            h_abs *= fmax(rk45::kMinFactor, rk45::kSafety * pow(error_norm, rk45::kErrorExponent));
-            rejected = true;
-        }
-        if (status) break;
-        const double t_old = t;
-        const double hd = t_new - t_old;
-        const double inv_hd = 1.0 / hd;
-        double Q[NS][rk45::kDenseOrder];
-#pragma unroll
-        for (int c = 0; c < NS; ++c)
-#pragma unroll
-            for (int q = 0; q < rk45::kDenseOrder; ++q) {
-                double s = K[0][c] * rk45::P[0][q];
-#pragma unroll
-                for (int j = 1; j <= rk45::kStages; ++j) s += K[j][c] * rk45::P[j][q];
-                Q[c][q] = hd * s;
-            }
-        static_assert(rk45::kDenseOrder == 4, "Horner form below is written for RK45's quartic");
-        const bool last = t_new - t_bound >= 0;
-        while (kk < a.t_n && (last || a.t_eval[kk] <= t_new)) {
-            const double x = (a.t_eval[kk] - t_old) * inv_hd;
-            double u[NS];
-#pragma unroll
-            for (int c = 0; c < NS; ++c)
-                u[c] = __builtin_fma(x, __builtin_fma(x, __builtin_fma(x, __builtin_fma(x, Q[c][3], Q[c][2]), Q[c][1]),
-                                                      Q[c][0]), y[c]);
-            const double r0 = a.y_obs[2 * kk] - u[0], r1 = a.y_obs[2 * kk + 1] - u[1];
-            const double z0 = r0 * a.U[0] + r1 * a.U[2];
-            const double z1 = r0 * a.U[1] + r1 * a.U[3];
-            ll += -0.5 * (a.c_log + (z0 * z0 + z1 * z1));
-            ++kk;
-        }
-        t = t_new;
-#pragma unroll
-        for (int c = 0; c < NS; ++c) { y[c] = y_new[c]; f[c] = f_new[c]; }
-    }
-    status_out = status;
+    const int status = lv_integrate<2>(th, p, [&](double t_old, double t_new, double inv_hd, const double* y,
+                                                  const double (*Q)[rk45::kDenseOrder], bool last) {
+        lv_observe<2>(p, kk, t_old, t_new, inv_hd, y, Q, last,
+                      [&](int k, const double* u) { ll += lv_loglik_term(p, k, u); });
+        return 0;
+    });
     if (status) return NAN;
-    double lp = -0.0;                 // np.sum(norm.logpdf(log_theta)), as lv_logdens_finish
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        const double x = lth[j];
-        lp += -(x * x) / 2.0 - a.norm_logc;
-    }
-    lp = 0.0 + lp;
-    return ll + lp;
+    return ll + lv_log_prior(lth, p.norm_logc);
 }
 
 // Philox4x64-10 (Random123; numpy/random/src/philox): one block for counter (c0, 0, 0, 0), key (k0, k1)
@@ -295,10 +146,7 @@ __global__ __launch_bounds__(kMcmcThreads) void lv_rwmh_kernel(LvMcmcArgs a) {
             ok = ok && isfinite(th[j]) && th[j] != 0.0;
         }
         double lp_new = NAN;
-        if (ok) {
-            int status = 0;
-            lp_new = lv_logdens_one(a, p, th, status);
-        }
+        if (ok) lp_new = lv_logdens_one(a.p, p, th);
         if (start) {
             lp = lp_new;
         } else {

@@ -166,21 +166,26 @@ int64_t mvt_moments_ws_bytes(int64_t n, int d);                            // ho
 hipError_t launch_mvt_moments(const MvtMomentsArgs& a, hipStream_t s);     // csrc/mvt_moments.hpp (in proxy.hip)
 int dist_tune(int value);    // st_tune key 13 (energy kernel variant)
 
-struct LvArgs {
-    const double* theta;      // (n, 4) row-major ODE parameters
-    const double* log_theta;  // (n, 4) row-major, log density only
-    int64_t n;
+// the Lotka-Volterra posterior and its RK45 settings, as every LV kernel reads them (csrc/lv_rk45.hpp)
+struct LvProblem {
     const double* t_eval;     // (t_n) ascending observation times
     int t_n;
     const double* y_obs;      // (t_n, 2) row-major observations
     double t0, t1;            // integration span
     double u0[2];             // initial state
     double rtol, atol;
-    double cinv[4];           // inv(C) row-major (gradient)
     double U[4];              // scipy _PSD(C).U row-major (log density)
     double c_log;             // rank * log(2 pi) + log_pdet of C
     double norm_logc;         // scipy.stats.norm's log(sqrt(2 pi))
     int64_t max_steps;
+};
+
+struct LvArgs {
+    const double* theta;      // (n, 4) row-major ODE parameters
+    const double* log_theta;  // (n, 4) row-major, log density only
+    int64_t n;
+    LvProblem p;
+    double cinv[4];           // inv(C) row-major (gradient)
     double* out;              // gradient: (n, 4); log density: (n)
     double* work;             // log density: (t_n, n) per-time terms
     int32_t* status;          // (n): 0 ok, 1 step size too small, 2 step limit reached
@@ -205,12 +210,7 @@ struct LvMcmcArgs {
     double* z;                // (chains, noise_ld, 4): read (mode 0) or written (mode 2)
     double* log_u;            // (chains, noise_ld)
     int64_t noise_ld, noise_row0;   // this launch's first step uses noise row noise_row0
-    const double* t_eval;     // (t_n) ascending observation times
-    int t_n;
-    const double* y_obs;      // (t_n, 2)
-    double t0, t1, u0[2], rtol, atol;
-    double U[4], c_log, norm_logc;  // as LvArgs
-    int64_t max_steps;
+    LvProblem p;
     double* samples;          // (chains, out_ld, 4)
     double* log_p;            // (chains, out_ld)
     int64_t out_ld, out_row0; // this launch's first step writes row out_row0

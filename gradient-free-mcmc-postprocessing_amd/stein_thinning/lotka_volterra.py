@@ -84,6 +84,15 @@ def _settings(data: LvData, rtol: float, atol: float):
     return t, y, s
 
 
+def _density_constants(data: LvData):
+    """(U, c_log, norm_logc) of the log target density: scipy's whitening factor of ``data.cov`` (``_PSD.U``),
+    rank * log(2 pi) + log_pdet, and ``scipy.stats._continuous_distns._norm_pdf_logC``."""
+    from .proxy import PsdFactor
+    psd = PsdFactor(np.asarray(data.cov, dtype=np.float64), allow_singular=False)
+    c_log = psd.rank * float(np.log(2 * np.pi)) + psd.log_pdet
+    return np.ascontiguousarray(psd.U, dtype=np.float64), c_log, float(np.log(np.sqrt(2 * np.pi)))
+
+
 def _status_check(status: np.ndarray, what: str):
     bad = np.flatnonzero(status)
     if bad.size:
@@ -137,15 +146,11 @@ def log_target_density(log_theta, data: Optional[LvData] = None, rtol: float = R
     """``lotka_volterra.log_target_density`` for every row of ``log_theta`` ((n, 4) or (4,)):
     returns (n,)."""
     import torch
-    from .proxy import PsdFactor
     data = reference_data() if data is None else data
     lth = _points(log_theta)
     th = np.exp(lth)                                   # as the reference: np.exp(log_theta)
     t, y, s = _settings(data, rtol, atol)
-    psd = PsdFactor(np.asarray(data.cov, dtype=np.float64), allow_singular=False)
-    c_log = psd.rank * float(np.log(2 * np.pi)) + psd.log_pdet
-    U = np.ascontiguousarray(psd.U, dtype=np.float64)
-    norm_logc = float(np.log(np.sqrt(2 * np.pi)))      # scipy.stats._continuous_distns._norm_pdf_logC
+    U, c_log, norm_logc = _density_constants(data)
     dev = nat.require_device()
     L = nat.lib()
     n = th.shape[0]
@@ -275,15 +280,11 @@ def rw_sample(log_theta_init, n_samples, step_size=0.0025, *, seed=None, noise=N
         raise ValueError('max_steps must be >= 1')
 
     import torch
-    from .proxy import PsdFactor
     data = reference_data() if data is None else data
     t, y, s = _settings(data, rtol, atol)
     if t.size < 1:
         raise ValueError('need at least one observation')
-    psd = PsdFactor(np.asarray(data.cov, dtype=np.float64), allow_singular=False)
-    c_log = psd.rank * float(np.log(2 * np.pi)) + psd.log_pdet
-    U = np.ascontiguousarray(psd.U, dtype=np.float64)
-    norm_logc = float(np.log(np.sqrt(2 * np.pi)))
+    U, c_log, norm_logc = _density_constants(data)
     dev = nat.require_device()
     L = nat.lib()
     td, yd = (torch.from_numpy(a).to(dev) for a in (t, y))

@@ -117,3 +117,21 @@ def fixed_reference():
     for a in res:
         a.setflags(write=False)
     return res
+
+
+FAIL_STEP, FAIL_SEED, FAIL_K = 0.3, 4, 1
+
+
+@functools.lru_cache(maxsize=None)
+def failing_input():
+    """The input of the failed-proposal tests: 4 chains of 21 rows from log(THETA), z = default_rng(FAIL_SEED)
+    .standard_normal((4, 20, 4)), log_u = -inf (a proposal that has a density is accepted, so a repeated row
+    marks a failure), proposal step FAIL_STEP, to be run with max_steps = FAIL_K more than the start row's
+    accepted-step count (23).  Chosen on the host among seeds 1 .. 5 and k = 0 .. 4 (tests/test_lv_mcmc_cpu.py
+    holds the conditions): 25 of the 80 proposals need more steps."""
+    x0 = np.tile(np.log(THETA), (4, 1))
+    z = np.random.default_rng(FAIL_SEED).standard_normal((4, 20, 4))
+    log_u = np.full((4, 20), -np.inf)
+    for a in (x0, z, log_u):
+        a.setflags(write=False)
+    return x0, z, log_u

@@ -164,3 +164,29 @@ def test_noise_moments(data):
     assert abs(u.mean() - 0.5) < 5.0 * np.sqrt(1.0 / 12.0 / u.size)
     assert np.all((u >= 0) & (u < 1))
     assert r.n_failed.sum() == 0
+
+
+def test_failed_proposals_are_those_log_target_density_fails(data):
+    """The sampler rejects a proposal for a failed integration exactly where log_target_density reports a
+    non-zero status (both run csrc/lv_rk45.hpp).  log_u = -inf accepts every proposal that has a density, so
+    a repeated row marks a failure; 25 of the 80 proposals need more than max_steps steps
+    (tests/test_lv_mcmc_cpu.py holds that from scipy alone)."""
+    import warnings
+    x0, z, log_u = M.failing_input()
+    max_steps = 23 + M.FAIL_K                          # 23: the start row's accepted steps
+    r = lv.rw_sample(x0, 21, M.FAIL_STEP, noise=(z, log_u), data=data, max_steps=max_steps)
+    proposals = r.samples[:, :-1] + M.FAIL_STEP * z    # x + step * z: one multiply, one add, as the kernel
+    with warnings.catch_warnings():
+        warnings.simplefilter('ignore', RuntimeWarning)
+        want = lv.log_target_density(proposals.reshape(-1, 4), data, max_steps=max_steps).reshape(4, 20)
+    bad = np.isnan(want)
+    print('failed proposals', bad.sum(axis=1).tolist())
+    assert 20 <= bad.sum() <= 60
+    repeats = np.all(r.samples[:, 1:] == r.samples[:, :-1], axis=2)
+    np.testing.assert_array_equal(repeats, bad)
+    np.testing.assert_array_equal(r.n_failed, bad.sum(axis=1))
+    np.testing.assert_array_equal(r.samples[:, 1:][~bad], proposals[~bad])
+    err = np.abs(r.log_p[:, 1:][~bad] - want[~bad]) / np.abs(want[~bad])
+    print('max rel diff to log_target_density', err.max())
+    assert err.max() < RTOL, err.max()
+    np.testing.assert_array_equal(r.log_p[:, 1:][bad], r.log_p[:, :-1][bad])

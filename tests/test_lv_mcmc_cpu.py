@@ -55,6 +55,37 @@ def test_moment_seed_passes_on_the_host_by_a_wide_margin():
     assert abs(u.mean() - 0.5) < 1.0 * np.sqrt(1.0 / 12.0 / u.size)
 
 
+def test_failing_input_fails_between_a_quarter_and_three_quarters():
+    """The conditions on the input of tests/test_gpu_lv_mcmc.py::
+    test_failed_proposals_are_those_log_target_density_fails, from scipy alone: the start passes, between 20
+    and 60 of the 80 proposals take more accepted steps than max_steps, theta stays finite and positive,
+    and no attempted step of any proposal has an error norm within 1e-5 of the accept threshold (so the
+    kernels' step counts are scipy's).  Recorded: start 23 steps, proposals 12 .. 45, 25 failures, smallest
+    margin 2.9e-3."""
+    from tests import lv_ref as R
+    x0, z, _ = M.failing_input()
+    max_steps = R.solution(M.THETA, sensitivity=False).accepted + M.FAIL_K
+    assert max_steps == 23 + M.FAIL_K
+    failed, margin, counts = 0, np.inf, []
+    for c in range(4):
+        x = x0[c]
+        for k in range(20):
+            p = x + M.FAIL_STEP * z[c, k]
+            with np.errstate(over='raise', under='raise'):
+                theta = np.exp(p)
+            assert np.all(np.isfinite(theta)) and np.all(theta > 0)
+            sol = R.solution(theta, sensitivity=False)
+            margin = min(margin, sol.margin)
+            counts.append(sol.accepted)
+            if sol.accepted > max_steps:
+                failed += 1
+            else:
+                x = p
+    print('failed', failed, 'of 80; accepted steps', min(counts), '..', max(counts), 'smallest margin', margin)
+    assert 20 <= failed <= 60, failed
+    assert margin > R.MARGIN_MIN, margin
+
+
 @pytest.fixture(scope='module')
 def lib():
     import __graft_entry__ as ge
