@@ -707,15 +707,15 @@ int64_t st_lv_rwmh_workspace_bytes(int64_t chains) {
     return chains * 64;
 }
 
-int st_lv_rwmh(double* state, int64_t chains, int64_t first_chain, int64_t first_step, int64_t steps,
-               int32_t init, const double* step_size, int32_t noise_mode, uint64_t seed, double* z,
-               double* log_u, int64_t noise_ld, int64_t noise_row0, const double* t_eval, int32_t t_n,
-               const double* y_obs, const double* span_u0_tol, const double* whiten, double c_log,
-               double norm_logc, int64_t max_steps, double* samples, double* log_p, int64_t out_ld,
-               int64_t out_row0, void* stream) {
+// st_lv_rwmh and st_lv_rwmh_wave: the checks (all before any HIP call) and the kernel arguments, once
+static int lv_rwmh_args(st::LvMcmcArgs& a, double* state, int64_t chains, int64_t first_chain, int64_t first_step,
+                        int64_t steps, int32_t init, const double* step_size, int32_t noise_mode, uint64_t seed,
+                        double* z, double* log_u, int64_t noise_ld, int64_t noise_row0, const double* t_eval,
+                        int32_t t_n, const double* y_obs, const double* span_u0_tol, const double* whiten,
+                        double c_log, double norm_logc, int64_t max_steps, double* samples, double* log_p,
+                        int64_t out_ld, int64_t out_row0) {
     if (chains < 1) return fail(ST_ERR_INVALID, "chains must be >= 1 (got %lld)", (long long)chains);
     if (steps < 1) return fail(ST_ERR_INVALID, "steps must be >= 1 (got %lld)", (long long)steps);
-    st::LvMcmcArgs a{};
     int rc = lv_problem(a.p, t_eval, t_n, y_obs, span_u0_tol, whiten, c_log, norm_logc, max_steps, true);
     if (rc) return rc;
     if (first_step < 1) return fail(ST_ERR_INVALID, "first_step must be >= 1 (got %lld)", (long long)first_step);
@@ -762,7 +762,35 @@ int st_lv_rwmh(double* state, int64_t chains, int64_t first_chain, int64_t first
     a.log_p = log_p;
     a.out_ld = out_ld;
     a.out_row0 = out_row0;
+    return ST_OK;
+}
+
+int st_lv_rwmh(double* state, int64_t chains, int64_t first_chain, int64_t first_step, int64_t steps,
+               int32_t init, const double* step_size, int32_t noise_mode, uint64_t seed, double* z,
+               double* log_u, int64_t noise_ld, int64_t noise_row0, const double* t_eval, int32_t t_n,
+               const double* y_obs, const double* span_u0_tol, const double* whiten, double c_log,
+               double norm_logc, int64_t max_steps, double* samples, double* log_p, int64_t out_ld,
+               int64_t out_row0, void* stream) {
+    st::LvMcmcArgs a{};
+    int rc = lv_rwmh_args(a, state, chains, first_chain, first_step, steps, init, step_size, noise_mode, seed, z,
+                          log_u, noise_ld, noise_row0, t_eval, t_n, y_obs, span_u0_tol, whiten, c_log, norm_logc,
+                          max_steps, samples, log_p, out_ld, out_row0);
+    if (rc) return rc;
     return hip_check(st::launch_lv_rwmh(a, static_cast<hipStream_t>(stream)), "lv rwmh launch");
+}
+
+int st_lv_rwmh_wave(double* state, int64_t chains, int64_t first_chain, int64_t first_step, int64_t steps,
+                    int32_t init, const double* step_size, int32_t noise_mode, uint64_t seed, double* z,
+                    double* log_u, int64_t noise_ld, int64_t noise_row0, const double* t_eval, int32_t t_n,
+                    const double* y_obs, const double* span_u0_tol, const double* whiten, double c_log,
+                    double norm_logc, int64_t max_steps, double* samples, double* log_p, int64_t out_ld,
+                    int64_t out_row0, void* stream) {
+    st::LvMcmcArgs a{};
+    int rc = lv_rwmh_args(a, state, chains, first_chain, first_step, steps, init, step_size, noise_mode, seed, z,
+                          log_u, noise_ld, noise_row0, t_eval, t_n, y_obs, span_u0_tol, whiten, c_log, norm_logc,
+                          max_steps, samples, log_p, out_ld, out_row0);
+    if (rc) return rc;
+    return hip_check(st::launch_lv_rwmh_wave(a, static_cast<hipStream_t>(stream)), "lv rwmh wave launch");
 }
 
 int st_greedy_finalize(const double* cands_in, int32_t nranks, int32_t d, uint32_t* idx_out,

@@ -208,6 +208,27 @@ __device__ __forceinline__ void lv_observe(const LvProblem& p, int& kk, double t
     }
 }
 
+// lv_observe for one of `stride` lanes that share an integration: the lane owns the points k, k + stride, ...
+// (its cursor k starts at its lane index) and tk holds p.t_eval[k] while k < p.t_n, loaded when the cursor
+// moves, so the test of the next step starts without a load.  The segment rule per point is lv_observe's,
+// x is formed from the same t_eval[k], so on_point sees the values lv_observe would hand it; with ascending
+// t_eval the lanes together consume exactly lv_observe's points of the step, each lane its own in increasing
+// k, and the lanes' trip counts differ by at most one.  No cross-lane operation.
+template <int NS, class OnPoint>
+__device__ __forceinline__ void lv_observe_strided(const LvProblem& p, int& k, double& tk, int stride, double t_old,
+                                                   double t_new, double inv_hd, const double* y_old,
+                                                   const double (*Q)[rk45::kDenseOrder], bool last,
+                                                   OnPoint&& on_point) {
+    while (k < p.t_n && (last || tk <= t_new)) {
+        const double x = (tk - t_old) * inv_hd;
+        double u[NS];
+        lv_horner<NS>(x, y_old, Q, u);
+        on_point(k, u);
+        k = p.t_n - k > stride ? k + stride : p.t_n;     // (no overflow for t_n near INT_MAX)
+        if (k < p.t_n) tk = p.t_eval[k];
+    }
+}
+
 // mvn.logpdf(y_k - u, 0, C) of observation k: -0.5 (c_log + |r U|^2)
 __device__ __forceinline__ double lv_loglik_term(const LvProblem& p, int k, const double* u) {
     const double r0 = p.y_obs[2 * k] - u[0], r1 = p.y_obs[2 * k + 1] - u[1];

@@ -216,6 +216,8 @@ struct LvMcmcArgs {
     int64_t out_ld, out_row0; // this launch's first step writes row out_row0
 };
 hipError_t launch_lv_rwmh(const LvMcmcArgs& a, hipStream_t s);
+// the same sampler with one wave per chain: the observation points of a step split over the 64 lanes
+hipError_t launch_lv_rwmh_wave(const LvMcmcArgs& a, hipStream_t s);
 
 hipError_t launch_greedy_rank_exchange(const double* recs, int K, int64_t stride, int d,
                                        const MailboxPeers& peers, int rank, int nranks, int64_t t,

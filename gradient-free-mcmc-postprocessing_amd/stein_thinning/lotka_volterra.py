@@ -188,6 +188,21 @@ def for_unique(func: Callable[[np.ndarray], np.ndarray], sample: np.ndarray) -> 
 # profiles/lv_mcmc_bench.json): one launch of 256 steps takes 0.180 s at 65 536 chains (0.70 ms per step, device
 # noise), 0.170 s at 4096 and 0.140 s at 5 -- under the quarter of a second a launch is meant to stay below.
 STEPS_PER_LAUNCH = 256
+# layout='wave' (one wave per chain, st_lv_rwmh_wave).  layout='auto' takes it for at most WAVE_MAX_CHAINS chains:
+# the largest chain count of the sweep 5, 64, 256, 1024, 4096 at which the wave layout is faster than the thread
+# layout by more than the spread of the windows.  Measured on MI355X (tools/lv_mcmc_bench.py,
+# profiles/lv_mcmc_wave_bench.json, 256 steps, supplied noise): wave / thread time 0.109 at 5 chains (0.056 against
+# 0.510 ms per step), 0.094, 0.093, 0.092 at 64, 256, 1024 and still 0.254 at 4096 (0.160 against 0.629 ms per
+# step), where the windows of either layout spread by 1 % (12 % for the thread layout at 5 chains).  More than 4096
+# chains were not measured in the wave layout: every wave repeats the integrator, so its time grows with the
+# chain count from 2048 waves on (two per SIMD) while the thread layout's stays flat up to 65 536 chains.
+# STEPS_PER_LAUNCH_WAVE: one launch of 256 steps at 4096 chains takes 0.044 s (device noise; 0.015 s at 5 chains),
+# under the quarter of a second with room for chains whose steps take twice as long (seen: 0.104 against 0.057 ms
+# per step for one of the reference's five starts); launches queue, so longer ones were not expected to gain.
+# Results do not depend on it.
+WAVE_MAX_CHAINS = 4096
+STEPS_PER_LAUNCH_WAVE = 256
+LAYOUTS = ('thread', 'wave', 'auto')
 
 
 @dataclass
@@ -209,10 +224,10 @@ def _is_tensor(a) -> bool:
 def rw_sample(log_theta_init, n_samples, step_size=0.0025, *, seed=None, noise=None,
               data: Optional[LvData] = None, rtol: float = RTOL, atol: float = ATOL, max_steps: int = MAX_STEPS,
               first_chain: int = 0, steps_per_launch: Optional[int] = None, return_noise: bool = False,
-              device_out: bool = False) -> RwSample:
-    """Random-walk Metropolis chains on the LV log posterior, one chain per GPU thread (``st_lv_rwmh``,
-    csrc/lv_mcmc.hip): the sampling stage of the reference's ``Sampling.ipynb`` (5 chains of 500 000 rows,
-    proposal step 0.0025, acceptance ~0.23), for as many chains as are given.
+              device_out: bool = False, layout: str = 'thread') -> RwSample:
+    """Random-walk Metropolis chains on the LV log posterior, one chain per GPU thread (``st_lv_rwmh``) or per
+    wave (``st_lv_rwmh_wave``; csrc/lv_mcmc.hip): the sampling stage of the reference's ``Sampling.ipynb``
+    (5 chains of 500 000 rows, proposal step 0.0025, acceptance ~0.23), for as many chains as are given.
 
     ``log_theta_init`` is (chains, 4) or (4,): the chains' starting rows (log theta).  Every chain gets
     ``n_samples`` rows, row 0 being its start.  The proposal is ``x + step_size * N(0, I)`` (``step_size`` a
@@ -235,8 +250,22 @@ def rw_sample(log_theta_init, n_samples, step_size=0.0025, *, seed=None, noise=N
     A proposal whose theta = exp(log theta) has a zero or non-finite component, or whose integration fails,
     is rejected and counted in ``n_failed``; a START whose own density fails raises ValueError.
     ``device_out=True`` returns ROCm tensors (for ``thin_chains`` / ``thin_gf`` without a host round trip).
-    ``steps_per_launch`` (default ``STEPS_PER_LAUNCH``) splits the run into launches; the result does not
-    depend on it."""
+    ``steps_per_launch`` (default ``STEPS_PER_LAUNCH``, ``STEPS_PER_LAUNCH_WAVE`` in the wave layout) splits the
+    run into launches; the result does not depend on it.
+
+    ``layout``: ``'thread'`` (default) runs one chain per GPU thread, the shape for thousands of chains.
+    ``'wave'`` runs one chain per wave of 64 lanes, the shape for a few long chains such as the reference's five:
+    every lane repeats the chain's proposal and RK45 integration and the observation points are split over the
+    lanes (point k goes to lane k mod 64).  ``'auto'`` takes ``'wave'`` for at most ``WAVE_MAX_CHAINS`` chains and
+    ``'thread'`` otherwise.  Everything above holds in both layouts.  Between the two, proposals and device
+    noise are bit-identical, and so is every per-point term of ``log_p``; only the order of their sum differs
+    (wave: each lane adds its points in increasing k, then the 64 partial sums are combined by an xor butterfly
+    with offsets 32 .. 1; an order that depends on t_n only), so ``log_p`` agrees to ~1e-13 relative (bit for bit
+    with at most 2 observation times) and the chains are equal row for row as long as no accept / reject
+    decision is closer than that.  A wave-layout chain is bit-identical to itself under any launch split, any
+    ``first_chain`` offset, with or without ``return_noise``, and when re-run from its recorded noise."""
+    if layout not in LAYOUTS:
+        raise ValueError(f'layout must be one of {LAYOUTS}, got {layout!r}')
     x0 = _points(log_theta_init)
     chains = x0.shape[0]
     if chains < 1:
@@ -272,7 +301,8 @@ def rw_sample(log_theta_init, n_samples, step_size=0.0025, *, seed=None, noise=N
         seed = int(seed)
     if isinstance(first_chain, bool) or int(first_chain) != first_chain or first_chain < 0:
         raise ValueError(f'first_chain must be an integer >= 0, got {first_chain!r}')
-    spl = STEPS_PER_LAUNCH if steps_per_launch is None else steps_per_launch
+    wave = layout == 'wave' or (layout == 'auto' and chains <= WAVE_MAX_CHAINS)
+    spl = (STEPS_PER_LAUNCH_WAVE if wave else STEPS_PER_LAUNCH) if steps_per_launch is None else steps_per_launch
     if isinstance(spl, bool) or int(spl) != spl or spl < 1:
         raise ValueError(f'steps_per_launch must be an integer >= 1, got {steps_per_launch!r}')
     spl = int(spl)
@@ -304,13 +334,15 @@ def rw_sample(log_theta_init, n_samples, step_size=0.0025, *, seed=None, noise=N
         zd = torch.empty((chains, steps, 4), dtype=torch.float64, device=dev)
         lud = torch.empty((chains, steps), dtype=torch.float64, device=dev)
     run = max(steps, 1)
+    name = 'st_lv_rwmh_wave' if wave else 'st_lv_rwmh'
+    entry = getattr(L, name)
     for k0 in range(0, run, spl):
         k = min(spl, run - k0)
-        nat.check(L.st_lv_rwmh(
+        nat.check(entry(
             nat.ptr(state), chains, int(first_chain), k0 + 1, k, 1 if k0 == 0 else 0, step.ctypes.data, mode,
             seed if noise is None else 0, nat.ptr(zd), nat.ptr(lud), max(steps, 1), k0, nat.ptr(td), t.size,
             nat.ptr(yd), s.ctypes.data, U.ctypes.data, c_log, norm_logc, int(max_steps), nat.ptr(samples),
-            nat.ptr(log_p), ld, k0 + 1, nat.stream_handle()), 'st_lv_rwmh')
+            nat.ptr(log_p), ld, k0 + 1, nat.stream_handle()), name)
     bad = torch.isnan(log_p[:, 0])
     if bool(bad.any()):
         first = int(torch.nonzero(bad)[0, 0])

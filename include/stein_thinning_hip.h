@@ -428,6 +428,23 @@ int st_lv_rwmh(double *state, int64_t chains, int64_t first_chain, int64_t first
                const double *y_obs, const double *span_u0_tol, const double *whiten, double c_log,
                double norm_logc, int64_t max_steps, double *samples, double *log_p, int64_t out_ld,
                int64_t out_row0, void *stream);
+/* The same sampler with one WAVE (64 lanes) per chain, for a few long chains (the reference's 5 chains of
+ * 500 000 rows): the arguments, the checks, the state record and the workspace of st_lv_rwmh, so launches of
+ * either entry point may continue a chain.  Every lane of a wave holds the chain's state, reads or draws the
+ * step's noise, forms the proposal and runs the RK45 integration (same inputs, same instructions); lane l
+ * evaluates the observation points k = l (mod 64), with st_lv_rwmh's per-point values bit for bit.
+ * Summation order (part of the contract): lane l adds its terms to 0.0 in increasing k; the 64 partial sums
+ * are combined by the xor butterfly v += shuffle_xor(v, off) for off = 32, 16, 8, 4, 2, 1; then the prior term
+ * is added.  The order depends on t_n only, never on the RK45 step sequence, the grid or the launch split.
+ * Bit-identical to st_lv_rwmh: proposals, device noise, and log_p for t_n <= 2 (the two orders coincide).
+ * For t_n >= 3 log_p differs by the summation order alone (~1e-13 relative), and the chains are equal row for
+ * row as long as no accept / reject decision is closer than that. */
+int st_lv_rwmh_wave(double *state, int64_t chains, int64_t first_chain, int64_t first_step, int64_t steps,
+                    int32_t init, const double *step_size, int32_t noise_mode, uint64_t seed, double *z,
+                    double *log_u, int64_t noise_ld, int64_t noise_row0, const double *t_eval, int32_t t_n,
+                    const double *y_obs, const double *span_u0_tol, const double *whiten, double c_log,
+                    double norm_logc, int64_t max_steps, double *samples, double *log_p, int64_t out_ld,
+                    int64_t out_row0, void *stream);
 
 /* ------------------------------------------------------------------------------------------
  * Integrand protocol -- replaces integrand(ind1, ind2) of the closures returned by

@@ -1,12 +1,21 @@
-"""Random-walk Metropolis sampler timings (st_lv_rwmh, csrc/lv_mcmc.hip); one JSON line, also written to --out;
-needs a GPU.
+"""Random-walk Metropolis sampler timings (st_lv_rwmh, st_lv_rwmh_wave, csrc/lv_mcmc.hip); one JSON line, also
+written to --out; needs a GPU.
 
 Per chain count (default 5, 4096, 65536), --steps Metropolis steps (default 256) from starts near log(THETA):
   * fused_device_s   -- one st_lv_rwmh launch, Philox noise drawn in the kernel;
   * fused_supplied_s -- one st_lv_rwmh launch reading z / log_u from device arrays;
   * yardstick_s      -- the same chains from what the library had before the sampler: per step one
                         st_lv_log_target_density launch (two kernels and a (t_n, chains) scratch array) plus torch
-                        elementwise propose / exp / accept on device tensors, on the same supplied noise.
+                        elementwise propose / exp / accept on device tensors, on the same supplied noise
+                        (--no-yardstick leaves this leg, its comparisons and the oracle timing out);
+  * wave_device_s, wave_supplied_s -- the two fused legs through st_lv_rwmh_wave (one wave per chain), for chain
+                        counts up to 4096 only: beyond that the replicated integrator makes a launch long.
+                        wave_over_thread_supplied / _device = wave time / fused time; wave_rows_equal: the share of
+                        rows on which the two layouts agree bit for bit on the same supplied noise;
+                        wave_max_abs_diff_log_p: the largest difference of log_p between them on such rows (the two
+                        summation orders).
+The record of the thread layout is profiles/lv_mcmc_bench.json (the defaults); the wave sweep is
+  --chains 5,64,256,1024,4096 --no-yardstick --out profiles/lv_mcmc_wave_bench.json
 Every window is the whole run of --steps steps between two device events with a synchronise on the second, after a
 warm-up of every leg; the legs alternate and the figure is the median of --reps windows.  chain_steps_s =
 chains * steps / time; ms_per_step = time / steps; yardstick_over_fused = yardstick_s / fused_supplied_s.
@@ -29,12 +38,16 @@ for p in (ROOT, os.path.join(ROOT, 'gradient-free-mcmc-postprocessing_amd')):
         sys.path.insert(0, p)
 
 
+WAVE_LEG_MAX_CHAINS = 4096
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--chains', default='5,4096,65536')
     ap.add_argument('--steps', type=int, default=256)
     ap.add_argument('--reps', type=int, default=3, help='timed windows per leg')
     ap.add_argument('--oracle-evals', type=int, default=20)
+    ap.add_argument('--no-yardstick', action='store_true', help='fused legs only (thread and wave layouts)')
     ap.add_argument('--out', default=os.path.join(ROOT, 'profiles', 'lv_mcmc_bench.json'))
     args = ap.parse_args()
 
@@ -78,7 +91,7 @@ def main():
         log_u = torch.rand((chains, steps), dtype=torch.float64, device=dev, generator=gen).log()
         res = {}
 
-        def fused(mode, name):
+        def fused(mode, name, entry='st_lv_rwmh'):
             state = torch.zeros((chains, 8), dtype=torch.float64, device=dev)
             samples = torch.empty((chains, steps + 1, 4), dtype=torch.float64, device=dev)
             log_p = torch.empty((chains, steps + 1), dtype=torch.float64, device=dev)
@@ -87,11 +100,11 @@ def main():
             def run():
                 state.zero_()
                 state[:, :4] = x0
-                nat.check(L.st_lv_rwmh(nat.ptr(state), chains, 0, 1, steps, 1, step.ctypes.data, mode, 1,
-                                       nat.ptr(z) if mode == 0 else None, nat.ptr(log_u) if mode == 0 else None, steps,
-                                       0, nat.ptr(td), t.size, nat.ptr(yd), s.ctypes.data, U.ctypes.data, c_log,
-                                       norm_logc, lv.MAX_STEPS, nat.ptr(samples), nat.ptr(log_p), steps + 1, 1, stream),
-                          'st_lv_rwmh')
+                nat.check(getattr(L, entry)(nat.ptr(state), chains, 0, 1, steps, 1, step.ctypes.data, mode, 1,
+                                            nat.ptr(z) if mode == 0 else None, nat.ptr(log_u) if mode == 0 else None,
+                                            steps, 0, nat.ptr(td), t.size, nat.ptr(yd), s.ctypes.data, U.ctypes.data,
+                                            c_log, norm_logc, lv.MAX_STEPS, nat.ptr(samples), nat.ptr(log_p),
+                                            steps + 1, 1, stream), entry)
             return run
 
         def yardstick():
@@ -125,8 +138,12 @@ def main():
                     samples[:, k + 1], log_p[:, k + 1] = x, lp
             return run
 
-        legs = {'fused_device_s': fused(1, 'fused_device_s'), 'fused_supplied_s': fused(0, 'fused_supplied_s'),
-                'yardstick_s': yardstick()}
+        legs = {'fused_device_s': fused(1, 'fused_device_s'), 'fused_supplied_s': fused(0, 'fused_supplied_s')}
+        if chains <= WAVE_LEG_MAX_CHAINS:
+            legs['wave_device_s'] = fused(1, 'wave_device_s', 'st_lv_rwmh_wave')
+            legs['wave_supplied_s'] = fused(0, 'wave_supplied_s', 'st_lv_rwmh_wave')
+        if not args.no_yardstick:
+            legs['yardstick_s'] = yardstick()
         for fn in legs.values():
             window(fn)
         times = {name: [] for name in legs}
@@ -140,32 +157,42 @@ def main():
             rec[key + '_min_s'], rec[key + '_max_s'] = min(v), max(v)
             rec[key + '_ms_per_step'] = rec[name] / steps * 1e3
             rec[key + '_chain_steps_s'] = chains * steps / rec[name]
-        rec['yardstick_over_fused'] = rec['yardstick_s'] / rec['fused_supplied_s']
         torch.cuda.synchronize()
         fs, fl, fstate = res['fused_supplied_s']
-        ys, yl, _ = res['yardstick_s']
-        rec['rows_equal'] = float((fs == ys).all(dim=2).double().mean())
-        # log_p of equal rows: the two summation orders.  The terms of the sum have both signs, so a chain that
-        # climbs through log_p = 0 has rows where the sum cancels: the difference is given in absolute terms, beside
-        # |log_p| of the row that holds the largest one and the largest |log_p| of the run
-        same = (fs == ys).all(dim=2)
-        diff = torch.where(same, (fl - yl).abs(), torch.zeros_like(fl))
-        worst = int(diff.argmax())
-        rec['max_abs_diff_log_p_on_equal_rows'] = float(diff.flatten()[worst])
-        rec['abs_log_p_at_that_row'] = float(yl.flatten()[worst].abs())
-        rec['max_abs_log_p'] = float(yl.abs().max())
         counts = fstate.view(torch.int64)
         rec['acceptance'] = float(counts[:, 5].double().mean()) / steps
         rec['n_failed'] = int(counts[:, 6].sum())
+        if 'wave_supplied_s' in legs:
+            rec['wave_over_thread_supplied'] = rec['wave_supplied_s'] / rec['fused_supplied_s']
+            rec['wave_over_thread_device'] = rec['wave_device_s'] / rec['fused_device_s']
+            ws, wl, wstate = res['wave_supplied_s']
+            same = (fs == ws).all(dim=2)
+            rec['wave_rows_equal'] = float(same.double().mean())
+            rec['wave_max_abs_diff_log_p'] = float(torch.where(same, (fl - wl).abs(), torch.zeros_like(fl)).max())
+            rec['wave_n_failed'] = int(wstate.view(torch.int64)[:, 6].sum())
+        if not args.no_yardstick:
+            rec['yardstick_over_fused'] = rec['yardstick_s'] / rec['fused_supplied_s']
+            ys, yl, _ = res['yardstick_s']
+            rec['rows_equal'] = float((fs == ys).all(dim=2).double().mean())
+            # log_p of equal rows: the two summation orders.  The terms of the sum have both signs, so a chain that
+            # climbs through log_p = 0 has rows where the sum cancels: the difference is given in absolute terms, beside
+            # |log_p| of the row that holds the largest one and the largest |log_p| of the run
+            same = (fs == ys).all(dim=2)
+            diff = torch.where(same, (fl - yl).abs(), torch.zeros_like(fl))
+            worst = int(diff.argmax())
+            rec['max_abs_diff_log_p_on_equal_rows'] = float(diff.flatten()[worst])
+            rec['abs_log_p_at_that_row'] = float(yl.flatten()[worst].abs())
+            rec['max_abs_log_p'] = float(yl.abs().max())
         out['shapes'].append(rec)
         del res, legs, z, log_u
 
-    lt = np.log(lv.THETA)
-    ol.log_target_density(lt, data.t, data.y, data.cov)
-    t0 = time.perf_counter()
-    for k in range(args.oracle_evals):
-        ol.log_target_density(lt + 1e-3 * k, data.t, data.y, data.cov)
-    out['oracle_eval_s'] = (time.perf_counter() - t0) / max(args.oracle_evals, 1)
+    if not args.no_yardstick:
+        lt = np.log(lv.THETA)
+        ol.log_target_density(lt, data.t, data.y, data.cov)
+        t0 = time.perf_counter()
+        for k in range(args.oracle_evals):
+            ol.log_target_density(lt + 1e-3 * k, data.t, data.y, data.cov)
+        out['oracle_eval_s'] = (time.perf_counter() - t0) / max(args.oracle_evals, 1)
     line = json.dumps(out)
     if args.out:
         os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
