@@ -293,7 +293,173 @@ __global__ __launch_bounds__(kWaveLanes * kWaveChainsPerBlock) void lv_rwmh_wave
     }
 }
 
+// ---- Metropolis-adjusted Langevin (MALA) sampler, one wave per chain ----
+// The chain runs in x = log theta.  The host hands over eps, h = 0.5 eps^2, w = 0.5 / eps^2 and the drift cap
+// c = drift_cap * eps (+inf: no cap) as doubles.  ONE 10-state integration (lv_integrate<10>: the system with
+// its forward sensitivities) at theta = exp(x) (the device's exp) gives u and J = du/dtheta at the observation
+// times, and from them
+//   lp(x)  = sum_k lv_loglik_term(k, u_k) + lv_log_prior(x)
+//   acc_j  = sum_k (J_k^T C^-1 (y_k - u_k))_j                        (lv_grad_term: lv_kernel<10>'s expression)
+//   g_j(x) = theta_j acc_j - x_j                                     (the gradient of lp with respect to x)
+// One Metropolis step, every operation uncontracted and in this order:
+//   d_j(x) = min(max(h_j g_j(x), -c_j), c_j)                         (a NaN stays a NaN)
+//   p_j    = (x_j + d_j(x)) + eps_j z_j
+//   rf_j   = (p_j - x_j) - d_j(x),   rr_j = (x_j - p_j) - d_j(p)
+//   qf     = sum_j w_j rf_j rf_j,    qr = sum_j w_j rr_j rr_j        (((w rf) rf), from 0.0, j ascending)
+//   accept exactly when log_u < (lp(p) - lp(x)) + (qf - qr)          (strict; a NaN anywhere rejects)
+// A theta with a zero or non-finite component, or an integration that ends with a non-zero status, rejects and
+// counts in n_failed.  Row t, log_p[t] and grad[t] = g(row t) are written for every row.
+// lp comes from the 10-state solution, whose RK45 step sequence is not the 2-state one of lv_rwmh*: the two
+// densities differ by the integrator's tolerance, not by rounding.
+// Layout, noise, init and the hand-off between launches are lv_rwmh_wave_kernel's; the state record has 16 words
+// per chain (x[4], lp, accepted, n_failed, one spare, g[4], four spare).
+// SUMMATION ORDER (part of the contract): lane l adds the terms of its points k = l (mod 64) to 0.0 in
+// increasing k over the whole integration -- one sum for ll, one for each acc_j; each of the five is then
+// combined by the xor butterfly v += shfl_xor(v, off), off = 32, 16, 8, 4, 2, 1; lp = that sum + lv_log_prior.
+// The order depends on t_n only.  For t_n <= 2 it is the time order ((0 + term_0) + term_1).  The butterflies run
+// once per Metropolis step, outside any data-dependent branch, also for a proposal rejected without
+// integrating; the decision is taken from lane 0's values (wave_first); lane 0 alone stores.
+__device__ __forceinline__ double mala_clip(double v, double c) {
+    v = v < -c ? -c : v;                  // (comparisons, not fmax / fmin: a NaN drift stays a NaN and rejects)
+    return v > c ? c : v;
+}
+
+template <bool DEVICE_NOISE, bool RECORD>
+__global__ __launch_bounds__(kWaveLanes * kWaveChainsPerBlock) void lv_mala_wave_kernel(LvMalaArgs a) {
+    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x / kWaveLanes));
+    const int lane = (int)(threadIdx.x % kWaveLanes);
+    const int64_t i = (int64_t)blockIdx.x * kWaveChainsPerBlock + wave;
+    if (i >= a.chains) return;            // the whole wave (partial last block)
+    double* st = a.state + 16 * i;
+    int64_t* sti = reinterpret_cast<int64_t*>(st);
+    double x[4], g[4], lp;
+    {
+        const double2* s2 = reinterpret_cast<const double2*>(st);
+        const double2 s0 = s2[0], s1 = s2[1], g0 = s2[4], g1 = s2[5];
+        x[0] = s0.x; x[1] = s0.y; x[2] = s1.x; x[3] = s1.y;
+        g[0] = g0.x; g[1] = g0.y; g[2] = g1.x; g[3] = g1.y;
+    }
+    lp = st[4];
+    int64_t accepted = sti[5], failed = sti[6];
+    double* rows = a.samples + (i * a.out_ld + a.out_row0) * 4;
+    double* grads = a.grad + (i * a.out_ld + a.out_row0) * 4;
+    double* lps = a.log_p + i * a.out_ld + a.out_row0;
+    double* zs = nullptr;
+    double* lus = nullptr;
+    if (!DEVICE_NOISE || RECORD) {
+        zs = a.z + (i * a.noise_ld + a.noise_row0) * 4;
+        lus = a.log_u + i * a.noise_ld + a.noise_row0;
+    }
+    const uint64_t chain = (uint64_t)(a.first_chain + i);
+    // k = -1: the start row itself (a.init), evaluated by the same code as every proposal
+#pragma unroll 1
+    for (int64_t k = a.init ? -1 : 0; k < a.steps; ++k) {
+        const bool start = k < 0;
+        double z[4] = {0.0, 0.0, 0.0, 0.0}, log_u = 0.0;
+        if (!start) {
+            if constexpr (DEVICE_NOISE) {
+                device_noise(a.seed, chain, (uint64_t)(a.first_step + k), z, log_u);
+                if constexpr (RECORD) {
+                    if (lane == 0) {
+                        reinterpret_cast<double2*>(zs + 4 * k)[0] = make_double2(z[0], z[1]);
+                        reinterpret_cast<double2*>(zs + 4 * k)[1] = make_double2(z[2], z[3]);
+                        lus[k] = log_u;
+                    }
+                }
+            } else {
+                const double2 z01 = reinterpret_cast<const double2*>(zs + 4 * k)[0];
+                const double2 z23 = reinterpret_cast<const double2*>(zs + 4 * k)[1];
+                z[0] = z01.x; z[1] = z01.y; z[2] = z23.x; z[3] = z23.y;
+                log_u = lus[k];
+            }
+        }
+        double d[4], p[4], th[4];
+        bool ok = true;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            d[j] = mala_clip(a.h[j] * g[j], a.clip[j]);
+            p[j] = start ? x[j] : (x[j] + d[j]) + a.eps[j] * z[j];
+            th[j] = exp(p[j]);
+            ok = ok && isfinite(th[j]) && th[j] != 0.0;
+        }
+        double ll = 0.0, acc[4] = {0.0, 0.0, 0.0, 0.0};     // this lane's terms, in increasing k
+        int status = 0;
+        if (ok) {
+            int kq = lane;
+            double tq = lane < a.p.t_n ? a.p.t_eval[lane] : 0.0;
+            status = lv_integrate<10>(th, a.p, [&](double t_old, double t_new, double inv_hd, const double* y,
+                                                   const double (*Q)[rk45::kDenseOrder], bool last) {
+                lv_observe_strided<10>(a.p, kq, tq, kWaveLanes, t_old, t_new, inv_hd, y, Q, last,
+                                       [&](int kk, const double* u) {
+                                           ll += lv_loglik_term(a.p, kk, u);
+                                           lv_grad_term(a.p, a.cinv, kk, u, acc);
+                                       });
+                return 0;
+            });
+        }
+#pragma unroll
+        for (int off = kWaveLanes / 2; off >= 1; off >>= 1) {
+            ll += __shfl_xor(ll, off);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) acc[j] += __shfl_xor(acc[j], off);
+        }
+        double lp_new = NAN, g_new[4] = {NAN, NAN, NAN, NAN};   // theta out of range, or the integration failed
+        if (ok && status == 0) {
+            lp_new = wave_first(ll) + lv_log_prior(p, a.p.norm_logc);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) g_new[j] = th[j] * wave_first(acc[j]) - p[j];
+        }
+        if (start) {
+            lp = lp_new;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) g[j] = g_new[j];
+        } else {
+            if (!(lp_new == lp_new)) ++failed;
+            double qf = 0.0, qr = 0.0;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const double rf = (p[j] - x[j]) - d[j];
+                const double rr = (x[j] - p[j]) - mala_clip(a.h[j] * g_new[j], a.clip[j]);
+                qf += a.w[j] * rf * rf;
+                qr += a.w[j] * rr * rr;
+            }
+            if (log_u < (lp_new - lp) + (qf - qr)) {
+#pragma unroll
+                for (int j = 0; j < 4; ++j) { x[j] = p[j]; g[j] = g_new[j]; }
+                lp = lp_new;
+                ++accepted;
+            }
+        }
+        if (lane == 0) {
+            reinterpret_cast<double2*>(rows + 4 * k)[0] = make_double2(x[0], x[1]);
+            reinterpret_cast<double2*>(rows + 4 * k)[1] = make_double2(x[2], x[3]);
+            reinterpret_cast<double2*>(grads + 4 * k)[0] = make_double2(g[0], g[1]);
+            reinterpret_cast<double2*>(grads + 4 * k)[1] = make_double2(g[2], g[3]);
+            lps[k] = lp;
+        }
+    }
+    if (lane == 0) {
+        double2* s2 = reinterpret_cast<double2*>(st);
+        s2[0] = make_double2(x[0], x[1]);
+        s2[1] = make_double2(x[2], x[3]);
+        s2[4] = make_double2(g[0], g[1]);
+        s2[5] = make_double2(g[2], g[3]);
+        st[4] = lp;
+        sti[5] = accepted;
+        sti[6] = failed;
+    }
+}
+
 }  // namespace
+
+hipError_t launch_lv_mala_wave(const LvMalaArgs& a, hipStream_t s) {
+    const unsigned blocks = (unsigned)((a.chains + kWaveChainsPerBlock - 1) / kWaveChainsPerBlock);
+    const unsigned threads = kWaveLanes * kWaveChainsPerBlock;
+    if (a.noise_mode == 0) lv_mala_wave_kernel<false, false><<<blocks, threads, 0, s>>>(a);
+    else if (a.noise_mode == 1) lv_mala_wave_kernel<true, false><<<blocks, threads, 0, s>>>(a);
+    else lv_mala_wave_kernel<true, true><<<blocks, threads, 0, s>>>(a);
+    return hipGetLastError();
+}
 
 hipError_t launch_lv_rwmh_wave(const LvMcmcArgs& a, hipStream_t s) {
     const unsigned blocks = (unsigned)((a.chains + kWaveChainsPerBlock - 1) / kWaveChainsPerBlock);

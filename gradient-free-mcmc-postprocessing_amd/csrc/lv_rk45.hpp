@@ -237,6 +237,18 @@ __device__ __forceinline__ double lv_loglik_term(const LvProblem& p, int k, cons
     return -0.5 * (p.c_log + (z0 * z0 + z1 * z1));
 }
 
+// the gradient's term of observation k, added to acc: acc[j] += (J_k^T C^-1 (y_k - u))_j with J_k = du/dtheta
+// = u[2 ..] (2 x 4, row-major) and cinv = inv(C) row-major -- the per-point expression of lv_kernel<10>
+// (lv.hip), operation for operation
+__device__ __forceinline__ void lv_grad_term(const LvProblem& p, const double cinv[4], int k, const double* u,
+                                             double acc[4]) {
+    const double r0 = p.y_obs[2 * k] - u[0], r1 = p.y_obs[2 * k + 1] - u[1];
+    const double g0 = cinv[0] * r0 + cinv[1] * r1;
+    const double g1 = cinv[2] * r0 + cinv[3] * r1;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) acc[j] += u[2 + j] * g0 + u[6 + j] * g1;
+}
+
 // log_prior = np.sum(norm.logpdf(log_theta))
 __device__ __forceinline__ double lv_log_prior(const double* log_theta, double norm_logc) {
     double lp = -0.0;

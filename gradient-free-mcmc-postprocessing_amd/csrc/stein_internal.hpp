@@ -219,6 +219,33 @@ hipError_t launch_lv_rwmh(const LvMcmcArgs& a, hipStream_t s);
 // the same sampler with one wave per chain: the observation points of a step split over the 64 lanes
 hipError_t launch_lv_rwmh_wave(const LvMcmcArgs& a, hipStream_t s);
 
+// Metropolis-adjusted Langevin sampler over the LV log posterior in x = log theta, one wave per chain
+// (csrc/lv_mcmc.hip: lv_mala_wave_kernel); the fields it shares with LvMcmcArgs mean the same
+struct LvMalaArgs {
+    double* state;            // (chains, 16) words: x[4], lp, accepted (int64), n_failed (int64), spare, g[4], 4 spare
+    int64_t chains;
+    int64_t first_chain;
+    int64_t first_step;
+    int64_t steps;
+    int init;
+    double eps[4];            // step size epsilon
+    double h[4];              // 0.5 eps^2, computed by the host
+    double w[4];              // 0.5 / eps^2, computed by the host
+    double clip[4];           // drift cap c = drift_cap * eps (> 0, may be +inf)
+    int noise_mode;
+    uint64_t seed;
+    double* z;
+    double* log_u;
+    int64_t noise_ld, noise_row0;
+    LvProblem p;
+    double cinv[4];           // inv(C) row-major
+    double* samples;          // (chains, out_ld, 4)
+    double* log_p;            // (chains, out_ld)
+    double* grad;             // (chains, out_ld, 4): the gradient of log p with respect to log theta
+    int64_t out_ld, out_row0;
+};
+hipError_t launch_lv_mala_wave(const LvMalaArgs& a, hipStream_t s);
+
 hipError_t launch_greedy_rank_exchange(const double* recs, int K, int64_t stride, int d,
                                        const MailboxPeers& peers, int rank, int nranks, int64_t t,
                                        double* recv, unsigned* status, hipStream_t s);

@@ -363,3 +363,170 @@ def rw_sample(log_theta_init, n_samples, step_size=0.0025, *, seed=None, noise=N
         res = RwSample(*(None if a is None else a.cpu().numpy() for a in
                          (res.samples, res.log_p, res.accepted, res.n_failed, res.z, res.log_u)))
     return res
+
+
+# Metropolis steps per launch of mala_sample.  Measured on MI355X (tools/lv_mala_bench.py, profiles/lv_mala_bench.json:
+# 256 steps as four launches of 64, device noise, eps 0.003, drift cap 1, starts near the mode): a launch of 64 steps
+# takes 0.046 s at 4096 chains, the largest count swept (0.72 ms per step), and 0.011-0.012 s at 5 to 1024 chains
+# (0.18 ms per step).  256 steps in one launch would take 0.185 s at 4096 chains -- under the quarter of a second a
+# launch is meant to stay below, but without room for chains whose integrations take twice the steps (seen in
+# rw_sample from one of the reference's starts), so 64 stays.  Launches queue behind one another; a different split
+# was not timed.  Results do not depend on it.
+STEPS_PER_LAUNCH_MALA = 64
+
+
+@dataclass
+class MalaSample:
+    """Result of ``mala_sample`` (NumPy arrays, or ROCm tensors with ``device_out=True``)."""
+    samples: object                   # (chains, n_samples, 4) log theta; row 0 is the start
+    log_p: object                     # (chains, n_samples) log target density of every row (10-state solution)
+    grad: object                      # (chains, n_samples, 4) gradient of log p with respect to log theta
+    accepted: object                  # (chains,) int64: accepted proposals
+    n_failed: object                  # (chains,) int64: proposals rejected without a density
+    z: object = None                  # (chains, n_samples - 1, 4): the normal noise used (return_noise)
+    log_u: object = None              # (chains, n_samples - 1): the log uniforms used (return_noise)
+
+
+def mala_sample(log_theta_init, n_samples, step_size, *, seed=None, noise=None, drift_cap: float = math.inf,
+                data: Optional[LvData] = None, rtol: float = RTOL, atol: float = ATOL, max_steps: int = MAX_STEPS,
+                first_chain: int = 0, steps_per_launch: Optional[int] = None, return_noise: bool = False,
+                device_out: bool = False) -> MalaSample:
+    """Metropolis-adjusted Langevin (MALA) chains on the LV log posterior, one chain per GPU wave
+    (``st_lv_mala_wave``, csrc/lv_mcmc.hip): the gradient-based stage of the reference's ``Sampling.ipynb``.  The
+    reference uses Stan's HMC there, which is not part of its tree, so the sampler is this project's own
+    definition.  Every row leaves with ``log_p`` and with ``grad`` = the gradient of log p with respect to
+    log theta -- the ``exp(samples) * grads`` the reference hands to ``thin`` -- so no separate
+    ``grad_log_posterior`` pass is needed: ``thin_chains(list(run.samples), list(run.grad), m)``.
+
+    Definition.  The chain runs in x = log theta; ``step_size`` is eps, a scalar or a (4,) vector (no default:
+    nothing in the reference fixes one; measured with the reference data, 5 chains of 256 steps from starts 0.02
+    off log(THETA) with ``drift_cap=1``: acceptance 0.98 at eps 0.0005, 0.73 at 0.001, 0.30 at 0.002, 0.15 at
+    0.003, 0.08 at 0.004 -- eps between 0.001 and 0.002 is usable, profiles/lv_mala_bench.json).  The host computes h = 0.5 eps eps, w = 0.5 / (eps eps) and
+    c = drift_cap eps once.  One 10-state RK45 integration at theta = exp(x) gives lp(x) (the terms of
+    ``log_target_density``) and g(x) = theta * sum_k J_k^T C^-1 (y_k - u_k) - x, which equals
+    ``exp(x) * grad_log_posterior(exp(x))`` to rounding.  A step proposes
+    ``p = (x + clip(h * g(x), -c, c)) + eps * z`` and accepts exactly when
+    ``log_u < (lp(p) - lp(x)) + (qf - qr)`` with qf = sum_j w_j rf_j rf_j, rf = (p - x) - d(x), and qr likewise
+    from rr = (x - p) - d(p); the comparison is strict and a NaN anywhere rejects.  ``drift_cap`` (> 0, default
+    inf: none) bounds every drift component at ``drift_cap * eps``; far from the mode the gradient is large and
+    an uncapped drift throws proposals to theta where the integration takes very long.
+
+    ``log_p`` comes from the 10-state solution, whose RK45 step sequence is not the 2-state one of
+    ``log_target_density`` / ``rw_sample``: the two differ by the integrator's tolerance (rtol 1e-3), not by
+    rounding (DESIGN.md section 17 has the figures).
+
+    Noise, ``seed``, ``noise=(z, log_u)``, ``first_chain``, ``return_noise``, ``device_out`` and the treatment of
+    failed proposals (``n_failed``) are ``rw_sample``'s: for one seed and chain id the noise is the same, bit for
+    bit.  A START whose own evaluation fails raises ValueError.  ``steps_per_launch`` (default
+    ``STEPS_PER_LAUNCH_MALA``) splits the run into launches; the result does not depend on it.  Lane l of a
+    chain's wave adds the observation points k = l (mod 64) in increasing k and the 64 partial sums are combined
+    by an xor butterfly (offsets 32 .. 1), for the density and for each gradient component; a chain is
+    bit-identical to itself under any launch split, any ``first_chain`` offset, with or without
+    ``return_noise``, and when re-run from its recorded noise."""
+    x0 = _points(log_theta_init)
+    chains = x0.shape[0]
+    if chains < 1:
+        raise ValueError('need at least one chain')
+    if not np.all(np.isfinite(x0)):
+        raise ValueError('log_theta_init must be finite')
+    if isinstance(n_samples, bool) or int(n_samples) != n_samples or n_samples < 1:
+        raise ValueError(f'n_samples must be an integer >= 1, got {n_samples!r}')
+    n_samples = int(n_samples)
+    steps = n_samples - 1
+    eps = np.asarray(step_size, dtype=np.float64)
+    if eps.ndim == 0:
+        eps = np.full(4, float(eps))
+    if eps.shape != (4,):
+        raise ValueError(f'step_size must be a scalar or (4,), got {eps.shape}')
+    if not np.all(np.isfinite(eps)) or np.any(eps <= 0):
+        raise ValueError(f'step_size must be finite and > 0, got {step_size!r}')
+    with np.errstate(over='ignore', divide='ignore'):
+        ehw = np.ascontiguousarray(np.concatenate([eps, 0.5 * eps * eps, 0.5 / (eps * eps)]))
+    if not np.all(np.isfinite(ehw)) or np.any(ehw <= 0):
+        raise ValueError(f'step_size {step_size!r}: 0.5 eps^2 and 0.5 / eps^2 must be finite and > 0')
+    try:
+        cap = float(drift_cap)
+    except (TypeError, ValueError):
+        raise ValueError(f'drift_cap must be a number > 0, got {drift_cap!r}') from None
+    if isinstance(drift_cap, bool) or not cap > 0:
+        raise ValueError(f'drift_cap must be > 0 (inf: no cap), got {drift_cap!r}')
+    clip = np.ascontiguousarray(cap * eps)
+    if noise is None and seed is None:
+        raise ValueError('give seed= (device noise) or noise=(z, log_u)')
+    if noise is not None and seed is not None:
+        raise ValueError('give either seed= or noise=(z, log_u), not both')
+    if noise is not None:
+        if not isinstance(noise, (tuple, list)) or len(noise) != 2:
+            raise ValueError('noise must be a pair (z, log_u)')
+        z_in, lu_in = (a if _is_tensor(a) else np.asarray(a, dtype=np.float64) for a in noise)
+        if tuple(z_in.shape) != (chains, steps, 4) or tuple(lu_in.shape) != (chains, steps):
+            raise ValueError(f'noise must be z ({chains}, {steps}, 4) and log_u ({chains}, {steps}), got '
+                             f'{tuple(z_in.shape)} and {tuple(lu_in.shape)}')
+    else:
+        if isinstance(seed, bool) or int(seed) != seed or not 0 <= int(seed) < 2 ** 64:
+            raise ValueError(f'seed must be an integer in [0, 2**64), got {seed!r}')
+        seed = int(seed)
+    if isinstance(first_chain, bool) or int(first_chain) != first_chain or first_chain < 0:
+        raise ValueError(f'first_chain must be an integer >= 0, got {first_chain!r}')
+    spl = STEPS_PER_LAUNCH_MALA if steps_per_launch is None else steps_per_launch
+    if isinstance(spl, bool) or int(spl) != spl or spl < 1:
+        raise ValueError(f'steps_per_launch must be an integer >= 1, got {steps_per_launch!r}')
+    spl = int(spl)
+    if max_steps < 1:
+        raise ValueError('max_steps must be >= 1')
+
+    import torch
+    data = reference_data() if data is None else data
+    t, y, s = _settings(data, rtol, atol)
+    if t.size < 1:
+        raise ValueError('need at least one observation')
+    U, c_log, norm_logc = _density_constants(data)
+    cinv = np.ascontiguousarray(np.linalg.inv(np.asarray(data.cov, dtype=np.float64)))
+    dev = nat.require_device()
+    L = nat.lib()
+    td, yd = (torch.from_numpy(a).to(dev) for a in (t, y))
+    state = torch.zeros((chains, 16), dtype=torch.float64, device=dev)  # counts: int64 zero = float 0.0 bits
+    state[:, :4] = torch.from_numpy(np.array(x0)).to(dev)          # (a copy: the caller's array may be read-only)
+    # n_samples = 1: the kernel runs at least one step; that step goes to a spare row and is dropped
+    ld = max(n_samples, 2)
+    samples = torch.empty((chains, ld, 4), dtype=torch.float64, device=dev)
+    grad = torch.empty((chains, ld, 4), dtype=torch.float64, device=dev)
+    log_p = torch.empty((chains, ld), dtype=torch.float64, device=dev)
+    mode, zd, lud = 1, None, None
+    if steps >= 1 and noise is not None:
+        mode = 0
+        zd, lud = (a.to(device=dev, dtype=torch.float64).contiguous() if _is_tensor(a)
+                   else torch.from_numpy(np.array(a, dtype=np.float64, order='C')).to(dev) for a in (z_in, lu_in))
+    elif steps >= 1 and return_noise:
+        mode = 2
+        zd = torch.empty((chains, steps, 4), dtype=torch.float64, device=dev)
+        lud = torch.empty((chains, steps), dtype=torch.float64, device=dev)
+    run = max(steps, 1)
+    for k0 in range(0, run, spl):
+        k = min(spl, run - k0)
+        nat.check(L.st_lv_mala_wave(
+            nat.ptr(state), chains, int(first_chain), k0 + 1, k, 1 if k0 == 0 else 0, ehw.ctypes.data,
+            clip.ctypes.data, mode, seed if noise is None else 0, nat.ptr(zd), nat.ptr(lud), max(steps, 1), k0,
+            nat.ptr(td), t.size, nat.ptr(yd), s.ctypes.data, U.ctypes.data, c_log, norm_logc, cinv.ctypes.data,
+            int(max_steps), nat.ptr(samples), nat.ptr(log_p), nat.ptr(grad), ld, k0 + 1, nat.stream_handle()),
+            'st_lv_mala_wave')
+    bad = torch.isnan(log_p[:, 0])
+    if bool(bad.any()):
+        first = int(torch.nonzero(bad)[0, 0])
+        raise ValueError(f'mala_sample: the evaluation of {int(bad.sum())} starting point(s) failed '
+                         f'(first: chain {first}): theta out of range or the RK45 integration did not finish')
+    counts = state.view(torch.int64)[:, 5:7]
+    if steps == 0:
+        counts = torch.zeros_like(counts)
+        samples, log_p, grad = samples[:, :1], log_p[:, :1], grad[:, :1]
+        if return_noise or noise is not None:
+            zd = torch.empty((chains, 0, 4), dtype=torch.float64, device=dev)
+            lud = torch.empty((chains, 0), dtype=torch.float64, device=dev)
+    accepted, failed = counts[:, 0].clone(), counts[:, 1].clone()
+    if not return_noise:
+        zd = lud = None
+    res = MalaSample(samples, log_p, grad, accepted, failed, zd, lud)
+    if not device_out:
+        res = MalaSample(*(None if a is None else a.cpu().numpy() for a in
+                           (res.samples, res.log_p, res.grad, res.accepted, res.n_failed, res.z, res.log_u)))
+    return res

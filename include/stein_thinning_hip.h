@@ -447,6 +447,52 @@ int st_lv_rwmh_wave(double *state, int64_t chains, int64_t first_chain, int64_t 
                     int64_t out_row0, void *stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Metropolis-adjusted Langevin (MALA) sampler for the LV log posterior, one WAVE per chain
+ * (csrc/lv_mcmc.hip: lv_mala_wave_kernel).  The reference's gradient-based sampler is Stan's HMC, which is not
+ * part of its tree; the sampler is this project's own definition:
+ *   The chain runs in x = log theta.  eps is the step size; the HOST computes h = 0.5 eps eps,
+ *   w = 0.5 / (eps eps) and c = drift_cap eps (+inf: no cap) once and hands them over as doubles.  All device
+ *   arithmetic below is uncontracted.  ONE 10-state RK45 integration (the system with its forward
+ *   sensitivities, as st_lv_grad_log_posterior) at theta = exp(x) (the device's exp) gives u and J = du/dtheta at
+ *   the observation times, and from them
+ *     lp(x)  = sum_k mvn.logpdf(y_k - u_k, 0, C) + sum_j norm.logpdf(x_j)   (the terms of st_lv_rwmh)
+ *     acc_j  = sum_k (J_k^T C^-1 (y_k - u_k))_j           (st_lv_grad_log_posterior's per-point expression)
+ *     g_j(x) = theta_j acc_j - x_j          (= exp(x) * grad_log_posterior(exp(x)) to rounding)
+ *   lp comes from the 10-state solution, whose step sequence is not the 2-state one of
+ *   st_lv_log_target_density / st_lv_rwmh: the two differ by the integrator's tolerance, not by rounding.
+ *   One Metropolis step at global step t = first_step + k:
+ *     d_j(x) = min(max(h_j g_j(x), -c_j), c_j)
+ *     p_j    = (x_j + d_j(x)) + eps_j z_j
+ *     rf_j   = (p_j - x_j) - d_j(x),   rr_j = (x_j - p_j) - d_j(p)
+ *     qf     = sum_j w_j rf_j rf_j,    qr = sum_j w_j rr_j rr_j     (each ((w rf) rf), from 0.0, j ascending)
+ *     accept exactly when log_u < (lp(p) - lp(x)) + (qf - qr)       (strict; a NaN anywhere rejects)
+ *   A theta with a zero or non-finite component, or an integration that ends with a non-zero status, rejects
+ *   and counts in n_failed.  Row out_row0 + k of samples, log_p and grad (= g of that row) is written.
+ * Layout: every lane of the wave holds the state (x, lp, g), forms the proposal and runs the integration; lane l
+ * evaluates the observation points k = l (mod 64).  Summation order (part of the contract): lane l adds its
+ * terms to 0.0 in increasing k -- one sum for the likelihood, one for each acc_j; each of the five is combined
+ * by the xor butterfly v += shuffle_xor(v, off) for off = 32, 16, 8, 4, 2, 1; then the prior term is added.  The
+ * order depends on t_n only, never on the RK45 step sequence, the grid or the launch split.
+ * Arguments as st_lv_rwmh_wave (noise modes, Philox keys and counters, init, first_step, first_chain, out_row0,
+ * noise_row0 included: for one seed the noise is st_lv_rwmh's), except:
+ *   state: st_lv_mala_workspace_bytes(chains) = 128 chains bytes, 16 words per chain: x[4], lp, accepted
+ *     (int64), n_failed (int64), one spare, g[4], four spare.
+ *   step_ehw: HOST (12) = eps[4], h[4], w[4];  drift_clip: HOST (4) = c (may be +inf);
+ *   cov_inv: HOST (2, 2) inv(C) row-major;  grad: (chains, out_ld, 4) device output.
+ * ST_ERR_INVALID (all checked before any HIP call): the conditions of st_lv_rwmh (eps is its step size); grad
+ * NULL or not 16-byte aligned; drift_clip or cov_inv NULL; an h or w that is not finite or <= 0; a c that is
+ * NaN or <= 0.
+ * ---------------------------------------------------------------------------------------- */
+int64_t st_lv_mala_workspace_bytes(int64_t chains);
+int st_lv_mala_wave(double *state, int64_t chains, int64_t first_chain, int64_t first_step, int64_t steps,
+                    int32_t init, const double *step_ehw, const double *drift_clip, int32_t noise_mode,
+                    uint64_t seed, double *z, double *log_u, int64_t noise_ld, int64_t noise_row0,
+                    const double *t_eval, int32_t t_n, const double *y_obs, const double *span_u0_tol,
+                    const double *whiten, double c_log, double norm_logc, const double *cov_inv,
+                    int64_t max_steps, double *samples, double *log_p, double *grad, int64_t out_ld,
+                    int64_t out_row0, void *stream);
+
+/* ------------------------------------------------------------------------------------------
  * Integrand protocol -- replaces integrand(ind1, ind2) of the closures returned by
  * stein_thinning.thinning._make_stein_integrand / _make_stein_gf_integrand and
  * stein_thinning.kernel.vfk0_imq (restated at JAX_Stein_Thinning.ipynb cell 27, json ~354-361;
