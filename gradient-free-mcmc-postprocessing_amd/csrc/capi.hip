@@ -707,8 +707,11 @@ int64_t st_lv_rwmh_workspace_bytes(int64_t chains) {
     return chains * 64;
 }
 
-// st_lv_rwmh and st_lv_rwmh_wave: the checks (all before any HIP call) and the kernel arguments, once
-static int lv_rwmh_args(st::LvMcmcArgs& a, double* state, int64_t chains, int64_t first_chain, int64_t first_step,
+// the LV samplers' common checks (all before any HIP call) and the kernel arguments that LvMcmcArgs and
+// LvMalaArgs share, once; step_size: the random walk's step, MALA's eps (checked here, copied by the caller)
+extern "C++" {
+template <class Args>
+static int lv_rwmh_args(Args& a, double* state, int64_t chains, int64_t first_chain, int64_t first_step,
                         int64_t steps, int32_t init, const double* step_size, int32_t noise_mode, uint64_t seed,
                         double* z, double* log_u, int64_t noise_ld, int64_t noise_row0, const double* t_eval,
                         int32_t t_n, const double* y_obs, const double* span_u0_tol, const double* whiten,
@@ -751,7 +754,6 @@ static int lv_rwmh_args(st::LvMcmcArgs& a, double* state, int64_t chains, int64_
     a.first_step = first_step;
     a.steps = steps;
     a.init = init;
-    for (int j = 0; j < 4; ++j) a.step[j] = step_size[j];
     a.noise_mode = noise_mode;
     a.seed = seed;
     a.z = z;
@@ -764,6 +766,7 @@ static int lv_rwmh_args(st::LvMcmcArgs& a, double* state, int64_t chains, int64_
     a.out_row0 = out_row0;
     return ST_OK;
 }
+}  // extern "C++"
 
 int st_lv_rwmh(double* state, int64_t chains, int64_t first_chain, int64_t first_step, int64_t steps,
                int32_t init, const double* step_size, int32_t noise_mode, uint64_t seed, double* z,
@@ -776,6 +779,7 @@ int st_lv_rwmh(double* state, int64_t chains, int64_t first_chain, int64_t first
                           log_u, noise_ld, noise_row0, t_eval, t_n, y_obs, span_u0_tol, whiten, c_log, norm_logc,
                           max_steps, samples, log_p, out_ld, out_row0);
     if (rc) return rc;
+    for (int j = 0; j < 4; ++j) a.step[j] = step_size[j];
     return hip_check(st::launch_lv_rwmh(a, static_cast<hipStream_t>(stream)), "lv rwmh launch");
 }
 
@@ -790,6 +794,7 @@ int st_lv_rwmh_wave(double* state, int64_t chains, int64_t first_chain, int64_t 
                           log_u, noise_ld, noise_row0, t_eval, t_n, y_obs, span_u0_tol, whiten, c_log, norm_logc,
                           max_steps, samples, log_p, out_ld, out_row0);
     if (rc) return rc;
+    for (int j = 0; j < 4; ++j) a.step[j] = step_size[j];
     return hip_check(st::launch_lv_rwmh_wave(a, static_cast<hipStream_t>(stream)), "lv rwmh wave launch");
 }
 
@@ -805,9 +810,9 @@ int st_lv_mala_wave(double* state, int64_t chains, int64_t first_chain, int64_t 
                     const double* whiten, double c_log, double norm_logc, const double* cov_inv,
                     int64_t max_steps, double* samples, double* log_p, double* grad, int64_t out_ld,
                     int64_t out_row0, void* stream) {
-    // st_lv_rwmh's checks (step_ehw[0 .. 3] = eps is its step size), then the sampler's own
-    st::LvMcmcArgs r{};
-    int rc = lv_rwmh_args(r, state, chains, first_chain, first_step, steps, init, step_ehw, noise_mode, seed, z,
+    // the common checks (step_ehw[0 .. 3] = eps is their step size), then the sampler's own
+    st::LvMalaArgs a{};
+    int rc = lv_rwmh_args(a, state, chains, first_chain, first_step, steps, init, step_ehw, noise_mode, seed, z,
                           log_u, noise_ld, noise_row0, t_eval, t_n, y_obs, span_u0_tol, whiten, c_log, norm_logc,
                           max_steps, samples, log_p, out_ld, out_row0);
     if (rc) return rc;
@@ -819,13 +824,6 @@ int st_lv_mala_wave(double* state, int64_t chains, int64_t first_chain, int64_t 
             return fail(ST_ERR_INVALID, "h and w of component %d must be finite and > 0 (got %g, %g)", j, h, w);
         if (!(c > 0)) return fail(ST_ERR_INVALID, "drift clip %d must be > 0 (got %g)", j, c);
     }
-    st::LvMalaArgs a{};
-    a.state = state;
-    a.chains = chains;
-    a.first_chain = first_chain;
-    a.first_step = first_step;
-    a.steps = steps;
-    a.init = init;
     for (int j = 0; j < 4; ++j) {
         a.eps[j] = step_ehw[j];
         a.h[j] = step_ehw[4 + j];
@@ -833,18 +831,7 @@ int st_lv_mala_wave(double* state, int64_t chains, int64_t first_chain, int64_t 
         a.clip[j] = drift_clip[j];
         a.cinv[j] = cov_inv[j];
     }
-    a.noise_mode = noise_mode;
-    a.seed = seed;
-    a.z = z;
-    a.log_u = log_u;
-    a.noise_ld = noise_ld;
-    a.noise_row0 = noise_row0;
-    a.p = r.p;
-    a.samples = samples;
-    a.log_p = log_p;
     a.grad = grad;
-    a.out_ld = out_ld;
-    a.out_row0 = out_row0;
     return hip_check(st::launch_lv_mala_wave(a, static_cast<hipStream_t>(stream)), "lv mala wave launch");
 }
 

@@ -450,32 +450,31 @@ __global__ __launch_bounds__(kWaveLanes * kWaveChainsPerBlock) void lv_mala_wave
     }
 }
 
+// kernel[noise_mode] (supplied, Philox, Philox + record) over a.chains chains, chains_per_block to a block
+template <class Args>
+hipError_t launch_noise_mode(void (*const (&kernel)[3])(Args), const Args& a, int chains_per_block,
+                             unsigned threads, hipStream_t s) {
+    const unsigned blocks = (unsigned)((a.chains + chains_per_block - 1) / chains_per_block);
+    kernel[a.noise_mode]<<<blocks, threads, 0, s>>>(a);
+    return hipGetLastError();
+}
+constexpr unsigned kWaveThreads = kWaveLanes * kWaveChainsPerBlock;
+
 }  // namespace
 
 hipError_t launch_lv_mala_wave(const LvMalaArgs& a, hipStream_t s) {
-    const unsigned blocks = (unsigned)((a.chains + kWaveChainsPerBlock - 1) / kWaveChainsPerBlock);
-    const unsigned threads = kWaveLanes * kWaveChainsPerBlock;
-    if (a.noise_mode == 0) lv_mala_wave_kernel<false, false><<<blocks, threads, 0, s>>>(a);
-    else if (a.noise_mode == 1) lv_mala_wave_kernel<true, false><<<blocks, threads, 0, s>>>(a);
-    else lv_mala_wave_kernel<true, true><<<blocks, threads, 0, s>>>(a);
-    return hipGetLastError();
+    return launch_noise_mode<LvMalaArgs>({lv_mala_wave_kernel<false, false>, lv_mala_wave_kernel<true, false>,
+                                          lv_mala_wave_kernel<true, true>}, a, kWaveChainsPerBlock, kWaveThreads, s);
 }
 
 hipError_t launch_lv_rwmh_wave(const LvMcmcArgs& a, hipStream_t s) {
-    const unsigned blocks = (unsigned)((a.chains + kWaveChainsPerBlock - 1) / kWaveChainsPerBlock);
-    const unsigned threads = kWaveLanes * kWaveChainsPerBlock;
-    if (a.noise_mode == 0) lv_rwmh_wave_kernel<false, false><<<blocks, threads, 0, s>>>(a);
-    else if (a.noise_mode == 1) lv_rwmh_wave_kernel<true, false><<<blocks, threads, 0, s>>>(a);
-    else lv_rwmh_wave_kernel<true, true><<<blocks, threads, 0, s>>>(a);
-    return hipGetLastError();
+    return launch_noise_mode<LvMcmcArgs>({lv_rwmh_wave_kernel<false, false>, lv_rwmh_wave_kernel<true, false>,
+                                          lv_rwmh_wave_kernel<true, true>}, a, kWaveChainsPerBlock, kWaveThreads, s);
 }
 
 hipError_t launch_lv_rwmh(const LvMcmcArgs& a, hipStream_t s) {
-    const unsigned blocks = (unsigned)((a.chains + kMcmcThreads - 1) / kMcmcThreads);
-    if (a.noise_mode == 0) lv_rwmh_kernel<false, false><<<blocks, kMcmcThreads, 0, s>>>(a);
-    else if (a.noise_mode == 1) lv_rwmh_kernel<true, false><<<blocks, kMcmcThreads, 0, s>>>(a);
-    else lv_rwmh_kernel<true, true><<<blocks, kMcmcThreads, 0, s>>>(a);
-    return hipGetLastError();
+    return launch_noise_mode<LvMcmcArgs>({lv_rwmh_kernel<false, false>, lv_rwmh_kernel<true, false>,
+                                          lv_rwmh_kernel<true, true>}, a, kMcmcThreads, kMcmcThreads, s);
 }
 
 }  // namespace st

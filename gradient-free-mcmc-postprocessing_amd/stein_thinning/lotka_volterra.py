@@ -221,6 +221,116 @@ def _is_tensor(a) -> bool:
     return type(a).__module__.startswith('torch')
 
 
+def _chain_start(log_theta_init, n_samples, step_size):
+    """Checked arguments every sampler starts from: the (chains, 4) starts, n_samples as an int, the (4,) step."""
+    x0 = _points(log_theta_init)
+    if x0.shape[0] < 1:
+        raise ValueError('need at least one chain')
+    if not np.all(np.isfinite(x0)):
+        raise ValueError('log_theta_init must be finite')
+    if isinstance(n_samples, bool) or int(n_samples) != n_samples or n_samples < 1:
+        raise ValueError(f'n_samples must be an integer >= 1, got {n_samples!r}')
+    step = np.asarray(step_size, dtype=np.float64)
+    if step.ndim == 0:
+        step = np.full(4, float(step))
+    if step.shape != (4,):
+        raise ValueError(f'step_size must be a scalar or (4,), got {step.shape}')
+    if not np.all(np.isfinite(step)) or np.any(step <= 0):
+        raise ValueError(f'step_size must be finite and > 0, got {step_size!r}')
+    return x0, int(n_samples), np.ascontiguousarray(step)
+
+
+def _chain_noise(chains, steps, seed, noise, first_chain, steps_per_launch, default_spl, max_steps):
+    """The samplers' remaining common checks: (seed as an int or None, noise as a pair (z, log_u) or None, steps
+    per launch)."""
+    if noise is None and seed is None:
+        raise ValueError('give seed= (device noise) or noise=(z, log_u)')
+    if noise is not None and seed is not None:
+        raise ValueError('give either seed= or noise=(z, log_u), not both')
+    if noise is not None:
+        if not isinstance(noise, (tuple, list)) or len(noise) != 2:
+            raise ValueError('noise must be a pair (z, log_u)')
+        noise = z_in, lu_in = [a if _is_tensor(a) else np.asarray(a, dtype=np.float64) for a in noise]
+        if tuple(z_in.shape) != (chains, steps, 4) or tuple(lu_in.shape) != (chains, steps):
+            raise ValueError(f'noise must be z ({chains}, {steps}, 4) and log_u ({chains}, {steps}), got '
+                             f'{tuple(z_in.shape)} and {tuple(lu_in.shape)}')
+    else:
+        if isinstance(seed, bool) or int(seed) != seed or not 0 <= int(seed) < 2 ** 64:
+            raise ValueError(f'seed must be an integer in [0, 2**64), got {seed!r}')
+        seed = int(seed)
+    if isinstance(first_chain, bool) or int(first_chain) != first_chain or first_chain < 0:
+        raise ValueError(f'first_chain must be an integer >= 0, got {first_chain!r}')
+    spl = default_spl if steps_per_launch is None else steps_per_launch
+    if isinstance(spl, bool) or int(spl) != spl or spl < 1:
+        raise ValueError(f'steps_per_launch must be an integer >= 1, got {steps_per_launch!r}')
+    if max_steps < 1:
+        raise ValueError('max_steps must be >= 1')
+    return seed, noise, int(spl)
+
+
+def _chain_problem(data, rtol, atol):
+    """The posterior as the samplers' entry points take it: (data, t, y, s, U, c_log, norm_logc), host values."""
+    data = reference_data() if data is None else data
+    t, y, s = _settings(data, rtol, atol)
+    if t.size < 1:
+        raise ValueError('need at least one observation')
+    return (data, t, y, s) + _density_constants(data)
+
+
+def _run_chains(*, failed_start, x0, n_samples, seed, noise, first_chain, spl, max_steps, problem, return_noise,
+                device_out, state_words, n_extra, launch):
+    """Run checked chains (``_chain_start``, ``_chain_noise``, ``_chain_problem``) on the device: returns samples,
+    log_p, ``n_extra`` further (chains, n_samples, 4) per-row outputs, accepted, n_failed, z, log_u.  The state
+    record has ``state_words`` words per chain.  ``launch(L, head=, mid=, rows=, extra=, tail=)`` makes one
+    entry-point call from the argument groups that every sampler's entry point has, in this order, between its own
+    (head: state .. init; mid: noise_mode .. norm_logc; rows: max_steps, samples, log_p; tail: out_ld ..)."""
+    import torch
+    _, t, y, s, U, c_log, norm_logc = problem
+    chains, steps = x0.shape[0], n_samples - 1
+    dev = nat.require_device()
+    L = nat.lib()
+    td, yd = (torch.from_numpy(a).to(dev) for a in (t, y))
+    state = torch.zeros((chains, state_words), dtype=torch.float64, device=dev)   # counts: int64 zero = float 0.0 bits
+    state[:, :4] = torch.from_numpy(np.array(x0)).to(dev)          # (a copy: the caller's array may be read-only)
+    # n_samples = 1: the kernel runs at least one step; that step goes to a spare row and is dropped
+    ld = max(n_samples, 2)
+    samples, *extra = (torch.empty((chains, ld, 4), dtype=torch.float64, device=dev) for _ in range(1 + n_extra))
+    log_p = torch.empty((chains, ld), dtype=torch.float64, device=dev)
+    mode, zd, lud = 1, None, None
+    if steps >= 1 and noise is not None:
+        mode = 0
+        zd, lud = (a.to(device=dev, dtype=torch.float64).contiguous() if _is_tensor(a)
+                   else torch.from_numpy(np.array(a, dtype=np.float64, order='C')).to(dev) for a in noise)
+    elif steps >= 1 and return_noise:
+        mode = 2
+        zd = torch.empty((chains, steps, 4), dtype=torch.float64, device=dev)
+        lud = torch.empty((chains, steps), dtype=torch.float64, device=dev)
+    run = max(steps, 1)
+    for k0 in range(0, run, spl):
+        k = min(spl, run - k0)
+        launch(L, head=(nat.ptr(state), chains, int(first_chain), k0 + 1, k, 1 if k0 == 0 else 0),
+               mid=(mode, seed if noise is None else 0, nat.ptr(zd), nat.ptr(lud), run, k0, nat.ptr(td), t.size,
+                    nat.ptr(yd), s.ctypes.data, U.ctypes.data, c_log, norm_logc),
+               rows=(int(max_steps), nat.ptr(samples), nat.ptr(log_p)), extra=[nat.ptr(e) for e in extra],
+               tail=(ld, k0 + 1, nat.stream_handle()))
+    bad = torch.isnan(log_p[:, 0])
+    if bool(bad.any()):
+        first = int(torch.nonzero(bad)[0, 0])
+        raise ValueError(f'{failed_start} of {int(bad.sum())} starting point(s) failed '
+                         f'(first: chain {first}): theta out of range or the RK45 integration did not finish')
+    counts = state.view(torch.int64)[:, 5:7]
+    if steps == 0:
+        counts = torch.zeros_like(counts)
+        samples, log_p, extra = samples[:, :1], log_p[:, :1], [e[:, :1] for e in extra]
+        if return_noise or noise is not None:
+            zd = torch.empty((chains, 0, 4), dtype=torch.float64, device=dev)
+            lud = torch.empty((chains, 0), dtype=torch.float64, device=dev)
+    if not return_noise:
+        zd = lud = None
+    res = (samples, log_p, *extra, counts[:, 0].clone(), counts[:, 1].clone(), zd, lud)
+    return res if device_out else tuple(None if a is None else a.cpu().numpy() for a in res)
+
+
 def rw_sample(log_theta_init, n_samples, step_size=0.0025, *, seed=None, noise=None,
               data: Optional[LvData] = None, rtol: float = RTOL, atol: float = ATOL, max_steps: int = MAX_STEPS,
               first_chain: int = 0, steps_per_launch: Optional[int] = None, return_noise: bool = False,
@@ -266,103 +376,18 @@ def rw_sample(log_theta_init, n_samples, step_size=0.0025, *, seed=None, noise=N
     ``first_chain`` offset, with or without ``return_noise``, and when re-run from its recorded noise."""
     if layout not in LAYOUTS:
         raise ValueError(f'layout must be one of {LAYOUTS}, got {layout!r}')
-    x0 = _points(log_theta_init)
-    chains = x0.shape[0]
-    if chains < 1:
-        raise ValueError('need at least one chain')
-    if not np.all(np.isfinite(x0)):
-        raise ValueError('log_theta_init must be finite')
-    if isinstance(n_samples, bool) or int(n_samples) != n_samples or n_samples < 1:
-        raise ValueError(f'n_samples must be an integer >= 1, got {n_samples!r}')
-    n_samples = int(n_samples)
-    steps = n_samples - 1
-    step = np.asarray(step_size, dtype=np.float64)
-    if step.ndim == 0:
-        step = np.full(4, float(step))
-    if step.shape != (4,):
-        raise ValueError(f'step_size must be a scalar or (4,), got {step.shape}')
-    if not np.all(np.isfinite(step)) or np.any(step <= 0):
-        raise ValueError(f'step_size must be finite and > 0, got {step_size!r}')
-    step = np.ascontiguousarray(step)
-    if noise is None and seed is None:
-        raise ValueError('give seed= (device noise) or noise=(z, log_u)')
-    if noise is not None and seed is not None:
-        raise ValueError('give either seed= or noise=(z, log_u), not both')
-    if noise is not None:
-        if not isinstance(noise, (tuple, list)) or len(noise) != 2:
-            raise ValueError('noise must be a pair (z, log_u)')
-        z_in, lu_in = (a if _is_tensor(a) else np.asarray(a, dtype=np.float64) for a in noise)
-        if tuple(z_in.shape) != (chains, steps, 4) or tuple(lu_in.shape) != (chains, steps):
-            raise ValueError(f'noise must be z ({chains}, {steps}, 4) and log_u ({chains}, {steps}), got '
-                             f'{tuple(z_in.shape)} and {tuple(lu_in.shape)}')
-    else:
-        if isinstance(seed, bool) or int(seed) != seed or not 0 <= int(seed) < 2 ** 64:
-            raise ValueError(f'seed must be an integer in [0, 2**64), got {seed!r}')
-        seed = int(seed)
-    if isinstance(first_chain, bool) or int(first_chain) != first_chain or first_chain < 0:
-        raise ValueError(f'first_chain must be an integer >= 0, got {first_chain!r}')
-    wave = layout == 'wave' or (layout == 'auto' and chains <= WAVE_MAX_CHAINS)
-    spl = (STEPS_PER_LAUNCH_WAVE if wave else STEPS_PER_LAUNCH) if steps_per_launch is None else steps_per_launch
-    if isinstance(spl, bool) or int(spl) != spl or spl < 1:
-        raise ValueError(f'steps_per_launch must be an integer >= 1, got {steps_per_launch!r}')
-    spl = int(spl)
-    if max_steps < 1:
-        raise ValueError('max_steps must be >= 1')
-
-    import torch
-    data = reference_data() if data is None else data
-    t, y, s = _settings(data, rtol, atol)
-    if t.size < 1:
-        raise ValueError('need at least one observation')
-    U, c_log, norm_logc = _density_constants(data)
-    dev = nat.require_device()
-    L = nat.lib()
-    td, yd = (torch.from_numpy(a).to(dev) for a in (t, y))
-    state = torch.zeros((chains, 8), dtype=torch.float64, device=dev)   # counts: int64 zero = float 0.0 bits
-    state[:, :4] = torch.from_numpy(np.array(x0)).to(dev)          # (a copy: the caller's array may be read-only)
-    # n_samples = 1: the kernel runs at least one step; that step goes to a spare row and is dropped
-    ld = max(n_samples, 2)
-    samples = torch.empty((chains, ld, 4), dtype=torch.float64, device=dev)
-    log_p = torch.empty((chains, ld), dtype=torch.float64, device=dev)
-    mode, zd, lud = 1, None, None
-    if steps >= 1 and noise is not None:
-        mode = 0
-        zd, lud = (a.to(device=dev, dtype=torch.float64).contiguous() if _is_tensor(a)
-                   else torch.from_numpy(np.array(a, dtype=np.float64, order='C')).to(dev) for a in (z_in, lu_in))
-    elif steps >= 1 and return_noise:
-        mode = 2
-        zd = torch.empty((chains, steps, 4), dtype=torch.float64, device=dev)
-        lud = torch.empty((chains, steps), dtype=torch.float64, device=dev)
-    run = max(steps, 1)
+    x0, n_samples, step = _chain_start(log_theta_init, n_samples, step_size)
+    wave = layout == 'wave' or (layout == 'auto' and x0.shape[0] <= WAVE_MAX_CHAINS)
+    seed, noise, spl = _chain_noise(x0.shape[0], n_samples - 1, seed, noise, first_chain, steps_per_launch,
+                                    STEPS_PER_LAUNCH_WAVE if wave else STEPS_PER_LAUNCH, max_steps)
     name = 'st_lv_rwmh_wave' if wave else 'st_lv_rwmh'
-    entry = getattr(L, name)
-    for k0 in range(0, run, spl):
-        k = min(spl, run - k0)
-        nat.check(entry(
-            nat.ptr(state), chains, int(first_chain), k0 + 1, k, 1 if k0 == 0 else 0, step.ctypes.data, mode,
-            seed if noise is None else 0, nat.ptr(zd), nat.ptr(lud), max(steps, 1), k0, nat.ptr(td), t.size,
-            nat.ptr(yd), s.ctypes.data, U.ctypes.data, c_log, norm_logc, int(max_steps), nat.ptr(samples),
-            nat.ptr(log_p), ld, k0 + 1, nat.stream_handle()), name)
-    bad = torch.isnan(log_p[:, 0])
-    if bool(bad.any()):
-        first = int(torch.nonzero(bad)[0, 0])
-        raise ValueError(f'rw_sample: the log target density of {int(bad.sum())} starting point(s) failed '
-                         f'(first: chain {first}): theta out of range or the RK45 integration did not finish')
-    counts = state.view(torch.int64)[:, 5:7]
-    if steps == 0:
-        counts = torch.zeros_like(counts)
-        samples, log_p = samples[:, :1], log_p[:, :1]
-        if return_noise or noise is not None:
-            zd = torch.empty((chains, 0, 4), dtype=torch.float64, device=dev)
-            lud = torch.empty((chains, 0), dtype=torch.float64, device=dev)
-    accepted, failed = counts[:, 0].clone(), counts[:, 1].clone()
-    if not return_noise:
-        zd = lud = None
-    res = RwSample(samples, log_p, accepted, failed, zd, lud)
-    if not device_out:
-        res = RwSample(*(None if a is None else a.cpu().numpy() for a in
-                         (res.samples, res.log_p, res.accepted, res.n_failed, res.z, res.log_u)))
-    return res
+
+    def launch(L, head, mid, rows, extra, tail):
+        nat.check(getattr(L, name)(*head, step.ctypes.data, *mid, *rows, *tail), name)
+    return RwSample(*_run_chains(
+        failed_start='rw_sample: the log target density', x0=x0, n_samples=n_samples, seed=seed, noise=noise,
+        first_chain=first_chain, spl=spl, max_steps=max_steps, problem=_chain_problem(data, rtol, atol),
+        return_noise=return_noise, device_out=device_out, state_words=8, n_extra=0, launch=launch))
 
 
 # Metropolis steps per launch of mala_sample.  Measured on MI355X (tools/lv_mala_bench.py, profiles/lv_mala_bench.json:
@@ -423,23 +448,7 @@ def mala_sample(log_theta_init, n_samples, step_size, *, seed=None, noise=None, 
     by an xor butterfly (offsets 32 .. 1), for the density and for each gradient component; a chain is
     bit-identical to itself under any launch split, any ``first_chain`` offset, with or without
     ``return_noise``, and when re-run from its recorded noise."""
-    x0 = _points(log_theta_init)
-    chains = x0.shape[0]
-    if chains < 1:
-        raise ValueError('need at least one chain')
-    if not np.all(np.isfinite(x0)):
-        raise ValueError('log_theta_init must be finite')
-    if isinstance(n_samples, bool) or int(n_samples) != n_samples or n_samples < 1:
-        raise ValueError(f'n_samples must be an integer >= 1, got {n_samples!r}')
-    n_samples = int(n_samples)
-    steps = n_samples - 1
-    eps = np.asarray(step_size, dtype=np.float64)
-    if eps.ndim == 0:
-        eps = np.full(4, float(eps))
-    if eps.shape != (4,):
-        raise ValueError(f'step_size must be a scalar or (4,), got {eps.shape}')
-    if not np.all(np.isfinite(eps)) or np.any(eps <= 0):
-        raise ValueError(f'step_size must be finite and > 0, got {step_size!r}')
+    x0, n_samples, eps = _chain_start(log_theta_init, n_samples, step_size)
     with np.errstate(over='ignore', divide='ignore'):
         ehw = np.ascontiguousarray(np.concatenate([eps, 0.5 * eps * eps, 0.5 / (eps * eps)]))
     if not np.all(np.isfinite(ehw)) or np.any(ehw <= 0):
@@ -451,82 +460,15 @@ def mala_sample(log_theta_init, n_samples, step_size, *, seed=None, noise=None, 
     if isinstance(drift_cap, bool) or not cap > 0:
         raise ValueError(f'drift_cap must be > 0 (inf: no cap), got {drift_cap!r}')
     clip = np.ascontiguousarray(cap * eps)
-    if noise is None and seed is None:
-        raise ValueError('give seed= (device noise) or noise=(z, log_u)')
-    if noise is not None and seed is not None:
-        raise ValueError('give either seed= or noise=(z, log_u), not both')
-    if noise is not None:
-        if not isinstance(noise, (tuple, list)) or len(noise) != 2:
-            raise ValueError('noise must be a pair (z, log_u)')
-        z_in, lu_in = (a if _is_tensor(a) else np.asarray(a, dtype=np.float64) for a in noise)
-        if tuple(z_in.shape) != (chains, steps, 4) or tuple(lu_in.shape) != (chains, steps):
-            raise ValueError(f'noise must be z ({chains}, {steps}, 4) and log_u ({chains}, {steps}), got '
-                             f'{tuple(z_in.shape)} and {tuple(lu_in.shape)}')
-    else:
-        if isinstance(seed, bool) or int(seed) != seed or not 0 <= int(seed) < 2 ** 64:
-            raise ValueError(f'seed must be an integer in [0, 2**64), got {seed!r}')
-        seed = int(seed)
-    if isinstance(first_chain, bool) or int(first_chain) != first_chain or first_chain < 0:
-        raise ValueError(f'first_chain must be an integer >= 0, got {first_chain!r}')
-    spl = STEPS_PER_LAUNCH_MALA if steps_per_launch is None else steps_per_launch
-    if isinstance(spl, bool) or int(spl) != spl or spl < 1:
-        raise ValueError(f'steps_per_launch must be an integer >= 1, got {steps_per_launch!r}')
-    spl = int(spl)
-    if max_steps < 1:
-        raise ValueError('max_steps must be >= 1')
+    seed, noise, spl = _chain_noise(x0.shape[0], n_samples - 1, seed, noise, first_chain, steps_per_launch,
+                                    STEPS_PER_LAUNCH_MALA, max_steps)
+    problem = _chain_problem(data, rtol, atol)
+    cinv = np.ascontiguousarray(np.linalg.inv(np.asarray(problem[0].cov, dtype=np.float64)))
 
-    import torch
-    data = reference_data() if data is None else data
-    t, y, s = _settings(data, rtol, atol)
-    if t.size < 1:
-        raise ValueError('need at least one observation')
-    U, c_log, norm_logc = _density_constants(data)
-    cinv = np.ascontiguousarray(np.linalg.inv(np.asarray(data.cov, dtype=np.float64)))
-    dev = nat.require_device()
-    L = nat.lib()
-    td, yd = (torch.from_numpy(a).to(dev) for a in (t, y))
-    state = torch.zeros((chains, 16), dtype=torch.float64, device=dev)  # counts: int64 zero = float 0.0 bits
-    state[:, :4] = torch.from_numpy(np.array(x0)).to(dev)          # (a copy: the caller's array may be read-only)
-    # n_samples = 1: the kernel runs at least one step; that step goes to a spare row and is dropped
-    ld = max(n_samples, 2)
-    samples = torch.empty((chains, ld, 4), dtype=torch.float64, device=dev)
-    grad = torch.empty((chains, ld, 4), dtype=torch.float64, device=dev)
-    log_p = torch.empty((chains, ld), dtype=torch.float64, device=dev)
-    mode, zd, lud = 1, None, None
-    if steps >= 1 and noise is not None:
-        mode = 0
-        zd, lud = (a.to(device=dev, dtype=torch.float64).contiguous() if _is_tensor(a)
-                   else torch.from_numpy(np.array(a, dtype=np.float64, order='C')).to(dev) for a in (z_in, lu_in))
-    elif steps >= 1 and return_noise:
-        mode = 2
-        zd = torch.empty((chains, steps, 4), dtype=torch.float64, device=dev)
-        lud = torch.empty((chains, steps), dtype=torch.float64, device=dev)
-    run = max(steps, 1)
-    for k0 in range(0, run, spl):
-        k = min(spl, run - k0)
-        nat.check(L.st_lv_mala_wave(
-            nat.ptr(state), chains, int(first_chain), k0 + 1, k, 1 if k0 == 0 else 0, ehw.ctypes.data,
-            clip.ctypes.data, mode, seed if noise is None else 0, nat.ptr(zd), nat.ptr(lud), max(steps, 1), k0,
-            nat.ptr(td), t.size, nat.ptr(yd), s.ctypes.data, U.ctypes.data, c_log, norm_logc, cinv.ctypes.data,
-            int(max_steps), nat.ptr(samples), nat.ptr(log_p), nat.ptr(grad), ld, k0 + 1, nat.stream_handle()),
-            'st_lv_mala_wave')
-    bad = torch.isnan(log_p[:, 0])
-    if bool(bad.any()):
-        first = int(torch.nonzero(bad)[0, 0])
-        raise ValueError(f'mala_sample: the evaluation of {int(bad.sum())} starting point(s) failed '
-                         f'(first: chain {first}): theta out of range or the RK45 integration did not finish')
-    counts = state.view(torch.int64)[:, 5:7]
-    if steps == 0:
-        counts = torch.zeros_like(counts)
-        samples, log_p, grad = samples[:, :1], log_p[:, :1], grad[:, :1]
-        if return_noise or noise is not None:
-            zd = torch.empty((chains, 0, 4), dtype=torch.float64, device=dev)
-            lud = torch.empty((chains, 0), dtype=torch.float64, device=dev)
-    accepted, failed = counts[:, 0].clone(), counts[:, 1].clone()
-    if not return_noise:
-        zd = lud = None
-    res = MalaSample(samples, log_p, grad, accepted, failed, zd, lud)
-    if not device_out:
-        res = MalaSample(*(None if a is None else a.cpu().numpy() for a in
-                           (res.samples, res.log_p, res.grad, res.accepted, res.n_failed, res.z, res.log_u)))
-    return res
+    def launch(L, head, mid, rows, extra, tail):
+        nat.check(L.st_lv_mala_wave(*head, ehw.ctypes.data, clip.ctypes.data, *mid, cinv.ctypes.data, *rows, *extra,
+                                    *tail), 'st_lv_mala_wave')
+    return MalaSample(*_run_chains(
+        failed_start='mala_sample: the evaluation', x0=x0, n_samples=n_samples, seed=seed, noise=noise,
+        first_chain=first_chain, spl=spl, max_steps=max_steps, problem=problem, return_noise=return_noise,
+        device_out=device_out, state_words=16, n_extra=1, launch=launch))
