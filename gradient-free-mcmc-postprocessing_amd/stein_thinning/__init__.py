@@ -9,5 +9,6 @@ RCCL): ``stein_thinning.distributed``.  Importing this package touches no GPU.
 from ._native import set_arithmetic  # noqa: F401
 from .naive import calculate_ksd_sets, naive_energy_curve, naive_idx, naive_ksd_curve  # noqa: F401
 from .thinning import set_dedup, set_rank_sharding, thin, thin_chains, thin_gf, thin_gf_chains  # noqa: F401
+from .thinning import thin_gf_many, thin_many  # noqa: F401
 
 __version__ = '0.1.0'

@@ -142,6 +142,13 @@ SIGNATURES = {
     'st_distance_sets_workspace_bytes': (_i64, [_i64, _i64, _i32]),
     'st_distance_sets': (ctypes.c_int, [_c_dp, _i64, _i64, _i32, _c_dp, _c_dp, _i64, _c_dp, _c_dp, _c_dp,
                                         _c_dp, _i64, _c_dp]),
+    # many chains in one launch (csrc/many.hip): row-major (chains, n, d) raw device arrays
+    'st_chain_stats': (ctypes.c_int, [_c_dp, _c_dp, _i64, _i64, _i32, _i32, _c_dp, _c_dp, _c_dp, _c_dp]),
+    'st_pdist_many': (ctypes.c_int, [_c_dp, _c_dp, _c_dp, _i64, _i64, _i32, _i64, _c_dp, _c_dp]),
+    'st_greedy_many': (ctypes.c_int, [_c_dp, _c_dp, _c_dp, _c_dp, _c_dp, _c_dp, _i64, _i64, _i32, _i64, _c_dp,
+                                      _c_dp, _c_dp]),
+    'st_greedy_many_max_n': (_i64, [_i32, _i32]),
+    'st_greedy_many_plan': (ctypes.c_int, [_i64, _i32, _i32, ctypes.POINTER(_i32), ctypes.POINTER(_i32)]),
 }
 ABI_VERSION = 1
 

@@ -37,10 +37,14 @@ def make_precon(sample: np.ndarray, preconditioner='id', on_device: bool = False
     return make_precon_rows(n, d, lambda rows: sample[rows], preconditioner, on_device)
 
 
-def make_precon_rows(n: int, d: int, rows_of, preconditioner='id', on_device: bool = False) -> np.ndarray:
+def make_precon_rows(n: int, d: int, rows_of, preconditioner='id', on_device: bool = False,
+                     med_squared=None) -> np.ndarray:
     """make_precon for an (n, d) sample given only ``rows_of(index array) -> those rows`` of it (the
-    median heuristic reads its subsample rows, nothing else)."""
+    median heuristic reads its subsample rows, nothing else).  ``med_squared``: the squared median
+    distance when the caller already holds it (thinning.thin_many takes every chain's on the device)."""
     def med2():
+        if med_squared is not None:
+            return med_squared
         idx = np.linspace(0, n - 1, MED_SUBSAMPLE, dtype=int) if n > MED_SUBSAMPLE else np.arange(n)
         sub = rows_of(idx)
         if on_device and 2 <= sub.shape[0] <= 65535:

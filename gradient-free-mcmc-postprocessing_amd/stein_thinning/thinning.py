@@ -653,3 +653,262 @@ def thin_gf(sample, log_p, log_q, gradient_q, n_points: int, standardize: bool =
         integrand = _make_stein_gf_integrand(sample, log_p, log_q, gradient_q, standardize, range_cap,
                                              preconditioner)
         return _greedy_search(n_points, integrand)
+
+
+# ---- many short chains in one launch (csrc/many.hip) ----------------------------------------------------
+
+last_engine: Optional[str] = None   # which path the last thin_many / thin_gf_many took: 'many' or 'chains'
+
+MANY_SORT_BYTES = 256 << 20   # distances sorted at a time by the 'med' median (torch.sort adds as much again
+                              # for its values and twice for its int64 indices: at most 4x this on the device)
+
+_STATUS_TEXT = {1: 'sample or gradient contains NaNs.', 2: 'sample or gradient contains infs.',
+                3: 'Too few unique samples in smp.'}
+
+
+def many_max_n(d: int, has_weights: bool = False) -> int:
+    """The longest chain the one-workgroup-per-chain engine takes at this d (0: d not supported)."""
+    from . import _native as nat
+    return int(nat.lib().st_greedy_many_max_n(int(d), 1 if has_weights else 0))
+
+
+def _many_engine_takes(n: int, d: int, preconditioner, has_weights: bool) -> bool:
+    if isinstance(preconditioner, str):
+        if preconditioner not in ('id', 'med', 'sclmed'):
+            return False
+        if preconditioner != 'id' and n < 2:   # no pair to take a median of: the loop's host route
+            return False
+    elif np.ndim(preconditioner) != 0:
+        return False
+    return d in (2, 4) and n <= many_max_n(d, has_weights)
+
+
+def _many_device_arrays(samples, gradients):
+    """(x, g, device): contiguous float64 (C, n, d) tensors on one device -- ROCm tensors as they are (no
+    copy when already float64 and contiguous), anything else uploaded to the engine's device."""
+    import torch
+    from . import _native as nat
+    if _on_device(samples):
+        dev = samples.device
+    elif _on_device(gradients):
+        dev = gradients.device
+    else:
+        dev = nat.require_device()
+
+    def put(a):
+        if not hasattr(a, 'detach'):
+            a = torch.from_numpy(np.ascontiguousarray(np.asarray(a, dtype=np.float64)))
+        return a.detach().to(device=dev, dtype=torch.float64).contiguous()
+    return put(samples), put(gradients), dev
+
+
+def _many_validate_shapes(samples, gradients):
+    """_validate_shapes for every chain of (C, n, d) arrays at once (the same messages)."""
+    ss, gs = tuple(samples.shape), tuple(gradients.shape)
+    if len(ss) != 3 or len(gs) != 3:
+        raise ValueError('sample or gradient is not two-dimensional.')
+    if ss[1] == 0 or ss[2] == 0:
+        raise ValueError('sample is empty.')
+    if gs != ss:
+        raise ValueError('Dimensions of sample and gradient are inconsistent.')
+    return ss
+
+
+def _many_stats(x, g, standardize: bool):
+    """st_chain_stats: (loc, scl, status) device tensors of the (C, n, d) device tensors x, g."""
+    import torch
+    from . import _native as nat
+    C, n, d = x.shape
+    loc = torch.empty((C, d), dtype=torch.float64, device=x.device)
+    scl = torch.empty((C, d), dtype=torch.float64, device=x.device)
+    status = torch.empty(C, dtype=torch.int32, device=x.device)
+    nat.check(nat.lib().st_chain_stats(nat.ptr(x), nat.ptr(g), C, n, d, 1 if standardize else 0, nat.ptr(loc),
+                                       nat.ptr(scl), nat.ptr(status), nat.stream_handle()), 'st_chain_stats')
+    return loc, scl, status
+
+
+def _many_medians(x, scl) -> np.ndarray:
+    """Per chain, np.median(pdist(sub-sample of x_c / scl_c)) as device.pdist_median takes it: st_pdist_many's
+    distances sorted on the device MANY_SORT_BYTES at a time, the middle value(s) averaged by np.mean."""
+    import torch
+    from . import _native as nat
+    from .kernel import MED_SUBSAMPLE
+    C, n, d = x.shape
+    sub = None
+    k = n
+    if n > MED_SUBSAMPLE:
+        k = MED_SUBSAMPLE
+        sub = torch.from_numpy(np.linspace(0, n - 1, MED_SUBSAMPLE, dtype=int).astype(np.int32)).to(x.device)
+    cnt = k * (k - 1) // 2
+    lo, hi = (cnt - 1) // 2, cnt // 2 + 1
+    per = max(1, min(C, MANY_SORT_BYTES // (cnt * 8)))
+    dist = torch.empty((per, cnt), dtype=torch.float64, device=x.device)
+    mids = []
+    for c0 in range(0, C, per):
+        c1 = min(C, c0 + per)
+        nat.check(nat.lib().st_pdist_many(nat.ptr(x[c0:c1]), nat.ptr(scl[c0:c1]), nat.ptr(sub), c1 - c0, n, d, k,
+                                          nat.ptr(dist), nat.stream_handle()), 'st_pdist_many')
+        mids.append(torch.sort(dist[:c1 - c0], dim=1).values[:, lo:hi].cpu())
+    mid = torch.cat(mids).numpy()
+    return np.array([np.mean(mid[c]) for c in range(C)])
+
+
+def _many_precon_scales(n: int, d: int, preconditioner, medians, ok=None):
+    """(linv_scale, linv_trace) per chain with thin()'s bits: kernel.make_precon's matrix, then
+    SteinIntegrand's isotropic_scale, from each chain's median (None: one preconditioner for all chains).
+    ``ok``: the chains whose input passed validation (the others keep l = tr = 1 and are reported by the
+    caller).  Returns (l, tr, first valid chain with a zero median or None)."""
+    from .device import isotropic_scale
+    from .kernel import make_precon_rows
+
+    def scale_of(med_squared):
+        iso = isotropic_scale(make_precon_rows(n, d, None, preconditioner, med_squared=med_squared))
+        if iso is None or not iso[0] > 0:
+            raise ValueError('preconditioner is not positive definite')
+        return iso
+    if medians is None:
+        l, tr = scale_of(None)
+        return np.full(1, l), np.full(1, tr), None
+    C = medians.shape[0]
+    l, tr = np.ones(C), np.ones(C)
+    bad = None
+    for c in range(C):
+        if ok is not None and not ok[c]:
+            continue
+        m2 = medians[c] ** 2
+        if m2 == 0:
+            bad = c if bad is None else bad
+            continue
+        l[c], tr[c] = scale_of(m2)
+    return l, tr, bad
+
+
+def _many_greedy(x, g, scl, weights, l, tr, n_points: int, want_sums: bool = False):
+    """st_greedy_many on device tensors: ((C, n_points) uint32 host array, the (C, n) final running sums as
+    a device tensor or None)."""
+    import torch
+    from . import _native as nat
+    C, n, d = x.shape
+    idx = torch.empty((C, n_points), dtype=torch.int32, device=x.device)
+    sums = torch.empty((C, n), dtype=torch.float64, device=x.device) if want_sums else None
+    nat.check(nat.lib().st_greedy_many(nat.ptr(x), nat.ptr(g), nat.ptr(scl), nat.ptr(weights), nat.ptr(l),
+                                       nat.ptr(tr), C, n, d, n_points, nat.ptr(idx), nat.ptr(sums),
+                                       nat.stream_handle()), 'st_greedy_many')
+    return idx.cpu().numpy().view(np.uint32).copy(), sums
+
+
+def _many_gf_weights(log_ps, log_qs, C: int, n: int, range_cap, stop: int):
+    """thin_gf's weights for chains [0, stop) -- _log_weights and np.exp per chain, its bits -- as a (C, n)
+    array; (weights, first error (chain, message) or None, first chain that drew the log-ratio warning)."""
+    log_ps = [_as_numpy(a).reshape(-1) for a in log_ps] if isinstance(log_ps, (list, tuple)) else _as_numpy(log_ps)
+    log_qs = [_as_numpy(a).reshape(-1) for a in log_qs] if isinstance(log_qs, (list, tuple)) else _as_numpy(log_qs)
+    if len(log_ps) != C or len(log_qs) != C:
+        raise ValueError('samples and gradients (and log densities) must have one entry per chain')
+    w = np.ones((C, n))
+    warned = None
+    with warnings.catch_warnings(record=True) as rec:
+        warnings.simplefilter('always')
+        for c in range(stop):
+            lp, lq = np.reshape(log_ps[c], -1), np.reshape(log_qs[c], -1)
+            if lp.shape[0] != n or lq.shape[0] != n:
+                return w, (c, 'Dimensions of sample and log densities are inconsistent.'), warned
+            if np.isnan(lp).any() or np.isnan(lq).any():
+                return w, (c, 'log_p or log_q contains NaNs.'), warned
+            w[c] = np.exp(_log_weights(lp, lq, range_cap))
+            if rec and warned is None:
+                warned = c
+    return w, None, warned
+
+
+def _thin_many_engine(samples, gradients, n_points, standardize, preconditioner, gf=None, want_sums=False):
+    """The one-workgroup-per-chain engine behind thin_many / thin_gf_many (``gf``: (log_ps, log_qs,
+    range_cap)).  Errors in the loop's order: chain 0's input, then n_points, then the other chains'."""
+    import torch
+    C, n, d = _many_validate_shapes(samples, gradients)
+    x, g, dev = _many_device_arrays(samples, gradients)
+    with torch.cuda.device(dev):
+        _, scl, status_d = _many_stats(x, g, standardize)
+        med = preconditioner in ('med', 'sclmed') if isinstance(preconditioner, str) else False
+        medians = _many_medians(x, scl) if med else None
+        status = status_d.cpu().numpy()
+        failed = np.flatnonzero(status)
+        err = (int(failed[0]), _STATUS_TEXT[int(status[failed[0]])]) if failed.size else None
+        weights = None
+        if gf is not None:
+            w, gf_err, warned = _many_gf_weights(gf[0], gf[1], C, n, gf[2], C if err is None else err[0])
+            if warned is not None:
+                warnings.warn(f'log_q differs from log_p by more than {WEIGHT_SCALE_THRESHOLD} '
+                              f'- consider using q that matches target better (chain {warned})')
+            err = gf_err if gf_err is not None else err
+            weights = torch.from_numpy(w).to(dev)
+
+        def raise_for(first_only: bool):
+            if err is not None and (err[0] == 0 or not first_only):
+                raise ValueError(f'{err[1]} (chain {err[0]})')
+        raise_for(True)
+        if medians is not None and status[0] == 0 and medians[0] == 0:
+            raise ValueError('Too few unique samples in smp. (chain 0)')
+        l, tr, zero = _many_precon_scales(n, d, preconditioner, medians, status == 0)
+        n_points = int(n_points)
+        if n_points < 0:
+            raise ValueError('negative dimensions are not allowed')
+        if n_points == 0:
+            raise IndexError('index 0 is out of bounds for axis 0 with size 0')
+        if zero is not None and (err is None or zero < err[0]):
+            raise ValueError(f'Too few unique samples in smp. (chain {zero})')
+        raise_for(False)
+        if l.shape[0] != C:
+            l, tr = np.full(C, l[0]), np.full(C, tr[0])
+        idx, sums = _many_greedy(x, g, scl, weights, torch.from_numpy(l).to(dev), torch.from_numpy(tr).to(dev),
+                                 n_points, want_sums)
+    return (idx, sums) if want_sums else idx
+
+
+def _many_chain_list(a):
+    return [a[c] for c in range(len(a))]
+
+
+def thin_many(samples, gradients, n_points: int, standardize: bool = True, preconditioner='id') -> np.ndarray:
+    """``np.stack([thin(samples[c], gradients[c], n_points, standardize, preconditioner) for c in range(C)])``
+    for C chains of the same length in ONE launch, one workgroup per chain (csrc/many.hip): the randomised-
+    starts experiment of the reference's report (report.tex:791) -- thousands of short chains sampled, each
+    thinned, the estimates compared.  ``samples`` / ``gradients``: (C, n, d) float64, NumPy arrays or ROCm
+    tensors (used in place on their device, never modified; neither x nor g visits the host: the column
+    statistics, the 'med' distances and the thin all run there).  Returns a (C, n_points) uint32 array.
+
+    'id', a number, 'med' and 'sclmed' run on this engine for d in {2, 4} and n <= many_max_n(d); 'smpcov', a
+    matrix, any other d or a longer chain go through thin_chains with the same result (``last_engine`` says
+    which path ran: 'many' or 'chains').  The engine evaluates every pair in the exact arithmetic (NumPy's
+    evaluation order), so set_arithmetic, set_dedup and the near-tie guard do not apply to it.  A NaN, an inf,
+    a zero scale or a zero median raises thin's ValueError for the lowest such chain, ' (chain c)' appended."""
+    global last_engine
+    C, n, d = _many_validate_shapes(samples, gradients)
+    if C == 0:
+        return np.empty((0, max(int(n_points), 0)), dtype=np.uint32)
+    if not _many_engine_takes(n, d, preconditioner, False):
+        last_engine = 'chains'
+        return np.stack(thin_chains(_many_chain_list(samples), _many_chain_list(gradients), n_points, standardize,
+                                    preconditioner))
+    last_engine = 'many'
+    return _thin_many_engine(samples, gradients, n_points, standardize, preconditioner)
+
+
+def thin_gf_many(samples, log_ps, log_qs, gradients_q, n_points: int, standardize: bool = True,
+                 range_cap: Optional[float] = None, preconditioner='id') -> np.ndarray:
+    """``np.stack([thin_gf(samples[c], log_ps[c], log_qs[c], gradients_q[c], n_points, ...) for c in
+    range(C)])`` in one launch (see thin_many: the same inputs, engine, fallback and errors).  ``log_ps`` /
+    ``log_qs``: (C, n); the weights are formed on the host per chain with thin_gf's own expressions, so their
+    bits are thin_gf's.  The log-ratio UserWarning is raised once, naming the first chain it applies to.
+    set_arithmetic, set_dedup and the near-tie guard do not apply."""
+    global last_engine
+    C, n, d = _many_validate_shapes(samples, gradients_q)
+    if C == 0:
+        return np.empty((0, max(int(n_points), 0)), dtype=np.uint32)
+    if not _many_engine_takes(n, d, preconditioner, True):
+        last_engine = 'chains'
+        return np.stack(thin_gf_chains(_many_chain_list(samples), _many_chain_list(log_ps), _many_chain_list(log_qs),
+                                       _many_chain_list(gradients_q), n_points, standardize, range_cap,
+                                       preconditioner))
+    last_engine = 'many'
+    return _thin_many_engine(samples, gradients_q, n_points, standardize, preconditioner,
+                             gf=(log_ps, log_qs, range_cap))

@@ -714,6 +714,54 @@ int st_layout_soa(const double *rowmajor, int64_t n, int32_t d, int64_t ld, doub
 int st_layout_soa_scaled(const double *rowmajor, int64_t n, int32_t d, int64_t ld, const double *scale,
                          int32_t divide, double *soa, void *stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Many short chains in one launch -- stein_thinning.thinning.thin_many / thin_gf_many: the loop
+ * [thin(s, g, m) for s, g in chains] (the reference's per-chain loop, Stein_thinning.ipynb cells
+ * 12-14; the randomised-starts experiment of report.tex:791) for `chains` chains of the same length,
+ * row-major (chains, n, d) RAW device arrays, one workgroup per chain and no traffic between the
+ * blocks.  These entry points read row-major arrays (not the SoA layout above); double arrays are
+ * 8-byte aligned, int32 / uint32 arrays 4-byte aligned.  ST_ERR_INVALID: a NULL or misaligned
+ * pointer, chains < 1, n < 1, d < 1, n_points < 1; ST_ERR_UNSUPPORTED: a d or n outside the stated
+ * range; either way nothing is enqueued.
+ * ---------------------------------------------------------------------------------------- */
+
+/* _validate_and_standardize's statistics per chain, bit-identical to NumPy: loc = np.mean(x_c, 0)
+ * (the sum over rows in row order, divided once by n), scl = np.mean(np.abs(x_c - loc), 0) (the same
+ * order, no fma), written to loc_out / scl_out (chains, d); status_out (chains) int32 with
+ * st_standardize_host's meaning and precedence: 0 ok, 1 a NaN in x or g, 2 an inf, 3 a zero scale.
+ * standardize = 0: scl = 1, loc = 0, finiteness only.  d = 2 .. 8 (d = 1: NumPy's pairwise sum of a
+ * contiguous column is st_standardize_host's). */
+int st_chain_stats(const double *x, const double *g, int64_t chains, int64_t n, int32_t d,
+                   int32_t standardize, double *loc_out, double *scl_out, int32_t *status_out,
+                   void *stream);
+
+/* st_pdist per chain on standardised rows: for chain c the condensed scipy pdist of the k rows
+ * x[c, sub_rows[0..k)] / scl[c] (sub_rows: k int32 row indices on the device, shared by all chains,
+ * entries outside [0, n) are clamped; NULL: all rows, k == n) into out + c k (k - 1) / 2.  Every
+ * value has the bits of st_pdist on x / scl (the 'med' / 'sclmed' median heuristic,
+ * kernel.make_precon).  2 <= k <= min(n, 65535), d <= 128, chains (k - 1) < 2^31. */
+int st_pdist_many(const double *x, const double *scl, const int32_t *sub_rows, int64_t chains,
+                  int64_t n, int32_t d, int64_t k, double *out, void *stream);
+
+/* The thin: for every chain the n_points indices _greedy_search selects on (x_c / scl_c,
+ * g_c * scl_c) -- the scaling applied on load with NumPy's bits -- with Gamma^-1 = linv_scale[c] I,
+ * linv_trace[c] = np.trace of it (device arrays of `chains` doubles), weights (chains, n) or NULL.
+ * One workgroup per chain: rows and running sums stay in registers for all steps; every pair in
+ * the EXACT arithmetic (NumPy's evaluation order, st_tune key 11 does not apply; no near-tie guard,
+ * no dedup).  idx_out (chains, n_points) uint32; a_out (chains, n) receives the final running sums,
+ * or NULL.  Bit model: oracle/stein_ref.c sr_greedy(arith = exact) per chain, idx and a_out.
+ * d in {2, 4} and n <= st_greedy_many_max_n(d, has_weights) (>= 4096), else ST_ERR_UNSUPPORTED;
+ * n_points > n and repeated selections are allowed. */
+int st_greedy_many(const double *x, const double *g, const double *scl, const double *weights,
+                   const double *linv_scale, const double *linv_trace, int64_t chains, int64_t n,
+                   int32_t d, int64_t n_points, uint32_t *idx_out, double *a_out, void *stream);
+/* host only: the largest n st_greedy_many takes at this d (0: d unsupported) */
+int64_t st_greedy_many_max_n(int32_t d, int32_t has_weights);
+/* host only: threads per block and rows per thread st_greedy_many uses at this n (tests place their
+ * shapes on both sides of every change) */
+int st_greedy_many_plan(int64_t n, int32_t d, int32_t has_weights, int32_t *threads_out,
+                        int32_t *rows_out);
+
 #ifdef __cplusplus
 }
 #endif
