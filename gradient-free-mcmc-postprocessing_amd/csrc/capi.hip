@@ -1,7 +1,11 @@
 // C ABI (include/stein_thinning_hip.h): argument validation, workspace carving, launch sequencing.
 // No allocation, no synchronisation: every entry point only enqueues work on the caller's stream.
+// Helpers (checks, argument builders, launch sequences, the bodies twin entry points share) come first, in the
+// anonymous namespace; extern "C" holds the entry points alone.  The ORDER of an entry point's checks is part of
+// the ABI: a call that violates two gets the first one's code.
 #include <math.h>
 #include <stdarg.h>
+#include <stdint.h>
 #include <stdio.h>
 #include <string.h>
 
@@ -26,6 +30,7 @@ int hip_check(hipError_t e, const char* what) {
 }
 
 bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
+bool aligned8(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 7u) == 0; }
 
 }  // namespace
 
@@ -35,6 +40,31 @@ int report_error(int code, const char* msg) { return fail(code, "%s", msg); }
 }  // namespace st
 
 namespace {
+
+// st_tune: who keeps a key's value: the greedy engine, the persistent engine, or a write-only setter of one key.
+// Every key number is named here and nowhere else in this file
+struct TuneKey {
+    enum { kGreedy, kPersistent, kSetter } owner;
+    int (*set)(int);   // kSetter only
+    bool read_only;
+};
+
+TuneKey tune_key(int32_t key) {
+    switch (key) {
+        case 7: return {TuneKey::kSetter, st::proxy_tune, false};
+        case 13: return {TuneKey::kSetter, st::dist_tune, false};
+        case 14: return {TuneKey::kSetter, st::dist_units_tune, false};
+        case 17: return {TuneKey::kSetter, st::lv_tune, false};
+        case 18: return {TuneKey::kSetter, st::lv_pieces_tune, false};
+        case 24: return {TuneKey::kSetter, st::kde_t_tune, false};
+        case 3: case 4: case 5: case 8: case 9: case 10: case 12: case 15: case 16: case 19: case 23:
+            return {TuneKey::kPersistent, nullptr, false};
+        default: {   // 100 .. 110: the calling thread's last plan; any other key is the greedy engine's to judge
+            const bool plan = key >= 100 && key <= 110;
+            return {plan ? TuneKey::kPersistent : TuneKey::kGreedy, nullptr, plan};
+        }
+    }
+}
 
 int check_problem(const double* x, const double* g, const double* w, int64_t n, int32_t d,
                   int64_t ld) {
@@ -68,6 +98,46 @@ int64_t greedy_ws_bytes(int32_t d) {
     return steps > persist ? steps : persist;
 }
 
+// output and workspace of a greedy entry point (d: checked before).  out: idx_out, or the candidate array of a
+// single-step entry point (which needs idx_out for t > 0 only and tests it itself); who: "" or
+// st_greedy_batch's "problem q: "
+int check_greedy_buffers(const char* who, const void* out, const double* a_work, const void* workspace,
+                         int64_t workspace_bytes, int32_t d) {
+    if (!out || !a_work || !workspace) return fail(ST_ERR_INVALID, "%sNULL output/workspace", who);
+    if (!aligned16(a_work) || !aligned16(workspace))
+        return fail(ST_ERR_INVALID, "%sa_work/workspace must be 16-byte aligned", who);
+    if (workspace_bytes < greedy_ws_bytes(d))
+        return fail(ST_ERR_INVALID, "%sworkspace too small (%lld < %lld)", who, (long long)workspace_bytes,
+                    (long long)greedy_ws_bytes(d));
+    return ST_OK;
+}
+
+int check_peers(void* const* peer_mailboxes, int32_t nranks, int32_t rank) {
+    if (nranks < 2 || nranks > st::kMailboxRanks)
+        return fail(ST_ERR_INVALID, "nranks must be in [2, %d]", st::kMailboxRanks);
+    if (rank < 0 || rank >= nranks) return fail(ST_ERR_INVALID, "rank out of range");
+    if (!peer_mailboxes) return fail(ST_ERR_INVALID, "NULL peer mailbox table");
+    for (int r = 0; r < nranks; ++r)
+        if (!peer_mailboxes[r] || !aligned16(peer_mailboxes[r]))
+            return fail(ST_ERR_INVALID, "peer mailbox %d is NULL or misaligned", r);
+    return ST_OK;
+}
+
+// set-batched forms: the checks both entry points share, after the problem's own: rows, offsets, sizes
+int check_sets(const int64_t* rows, const int64_t* set_offsets, int64_t n_sets) {
+    if (!rows || !set_offsets) return fail(ST_ERR_INVALID, "rows/set_offsets pointer is NULL");
+    if (!aligned8(rows) || !aligned8(set_offsets)) return fail(ST_ERR_INVALID, "rows/set_offsets must be 8-byte aligned");
+    switch (st::sets_check_offsets(set_offsets, n_sets)) {
+        case 1: return fail(ST_ERR_INVALID, "set_offsets[0] must be 0 (got %lld)", (long long)set_offsets[0]);
+        case 2: return fail(ST_ERR_INVALID, "set_offsets must not decrease");
+        case 3: return fail(ST_ERR_INVALID, "empty index set");
+        default: break;
+    }
+    if (n_sets > 0x7FFFFFFFll || st::sets_item_count(set_offsets, n_sets) > 0x7FFFFFFFll)
+        return fail(ST_ERR_UNSUPPORTED, "too many sets / column blocks for one grid");
+    return ST_OK;
+}
+
 double* bank(void* ws, int32_t d, int b) {
     return reinterpret_cast<double*>(static_cast<char*>(ws) + st::kWsControlBytes) +
            (int64_t)b * st::kMaxBlocks * st::cand_stride(d);
@@ -82,6 +152,311 @@ st::GreedyArgs make_args(const double* x, const double* g, const double* w, int6
     a.rec_stride = st::cand_stride(d);
     a.compact = st::arith_compact();
     return a;
+}
+
+// one step of a run that the caller distributes over ranks (st_greedy_step, st_greedy_step_exchange): the
+// shard at row_offset reads the ranks' records of step t - 1 and leaves its blocks' records in bank 0
+st::GreedyArgs step_args(const double* x, const double* g, const double* w, int64_t n, int32_t d, int64_t ld,
+                         double l, double tr, int64_t row_offset, int64_t t, const double* recs_in, int32_t nranks,
+                         uint32_t* idx_out, double* a_work, void* workspace) {
+    st::GreedyArgs a = make_args(x, g, w, n, d, ld, l, tr, a_work);
+    a.row_offset = row_offset;
+    a.t = t;
+    a.recs_in = recs_in;
+    a.nrecs_in = nranks;
+    a.recs_out = bank(workspace, d, 0);
+    a.idx_out = idx_out;
+    return a;
+}
+
+// peers: the ranks' mailboxes, or NULL (a plan-only query: no peer is touched)
+st::RankSpec rank_spec(int64_t row_begin, int64_t row_end, int32_t rank, int32_t nranks, uint64_t seq_base,
+                       void* inbox, void* const* peers) {
+    st::RankSpec rs{};
+    rs.row_begin = row_begin;
+    rs.row_end = row_end;
+    rs.rank = rank;
+    rs.nranks = nranks;
+    rs.seq_base = seq_base;
+    rs.inbox = static_cast<uint64_t*>(inbox);
+    for (int r = 0; peers && r < nranks; ++r) rs.peer[r] = static_cast<uint64_t*>(peers[r]);
+    return rs;
+}
+
+st::MailboxPeers mailbox_peers(void* const* peer_mailboxes, int32_t nranks) {
+    st::MailboxPeers peers{};
+    for (int r = 0; r < nranks; ++r) peers.p[r] = static_cast<uint64_t*>(peer_mailboxes[r]);
+    return peers;
+}
+
+// a run starts: no near-tie word of an earlier run may survive (the step kernels run unguarded: -2)
+int reset_near_tie(void* workspace, hipStream_t s) {
+    return hip_check(hipMemsetAsync(static_cast<char*>(workspace) + st::kWsTieOff, 0,
+                                    (size_t)(st::kWsBoundsOff + 40 - st::kWsTieOff), s),
+                     "near-tie words reset");
+}
+
+// steps [t_begin, t_end) of a run of n_points, one launch each, through the two record banks; then the
+// finalize launch if that completes the run.  Dense preconditioner (a.linv set): its own grid, and its own
+// launcher after the diagonal step (t = 0, shared)
+int run_steps(st::GreedyArgs& a, void* workspace, int64_t t_begin, int64_t t_end, int64_t n_points,
+              hipStream_t s) {
+    const bool dense = a.linv != nullptr;
+    const int blocks = dense ? st::greedy_dense_blocks(a.n, a.d) : st::greedy_blocks(a.n, a.d);
+    int rc = t_begin == 0 ? reset_near_tie(workspace, s) : ST_OK;
+    if (rc) return rc;
+    for (int64_t t = t_begin; t < t_end; ++t) {
+        a.t = t;
+        a.recs_in = bank(workspace, a.d, (int)((t + 1) & 1));
+        a.nrecs_in = blocks;
+        a.recs_out = bank(workspace, a.d, (int)(t & 1));
+        rc = hip_check(dense && t > 0 ? st::launch_greedy_step_dense(a, blocks, s)
+                                      : st::launch_greedy_step(a, t == 0, blocks, s),
+                       dense ? "dense greedy step launch" : "greedy step launch");
+        if (rc) return rc;
+    }
+    if (t_end < n_points || t_end == t_begin) return ST_OK;
+    return hip_check(st::launch_greedy_finalize(bank(workspace, a.d, (int)((n_points - 1) & 1)), blocks,
+                                                a.rec_stride, a.idx_out, n_points - 1, s),
+                     "greedy finalize launch");
+}
+
+// diagonal / dense twins: dense = the (d, d) array linv and l = 0; else linv = NULL and the scale l
+int kernel_pairs(const double* x, const double* g, const double* w, int64_t ld, int32_t d, bool dense,
+                 const double* linv, double l, double tr, const int64_t* i1, const int64_t* i2, int64_t n_pairs,
+                 double* out, void* stream) {
+    if (n_pairs == 0) return ST_OK;
+    if (!x || !g) return fail(ST_ERR_INVALID, "sample/gradient pointer is NULL");
+    if (dense) {
+        if (d < 1) return fail(ST_ERR_INVALID, "d must be >= 1 (got %d)", d);
+        int rc = check_dense(linv, d);
+        if (rc) return rc;
+    } else if (d < 1 || d > st::kMaxDim) {
+        return fail(ST_ERR_UNSUPPORTED, "unsupported d = %d", d);
+    }
+    if (ld < 1) return fail(ST_ERR_INVALID, "ld must be >= 1");
+    if (n_pairs < 0 || !i1 || !i2 || !out) return fail(ST_ERR_INVALID, "bad pair list");
+    return hip_check(st::launch_pairs(st::PairArgs{x, g, w, ld, d, l, tr, linv}, i1, i2, n_pairs, out,
+                                      static_cast<hipStream_t>(stream)),
+                     dense ? "dense pairs launch" : "pairs launch");
+}
+
+int ksd_cumulative(const double* x, const double* g, const double* w, int64_t m, int64_t ld, int32_t d, bool dense,
+                   const double* linv, double l, double tr, double* ks_out, void* workspace,
+                   int64_t workspace_bytes, void* stream) {
+    int rc = check_problem(x, g, w, m, d, ld);
+    if (rc) return rc;
+    if (dense) rc = check_dense(linv, d);
+    if (rc) return rc;
+    if (!ks_out || !workspace) return fail(ST_ERR_INVALID, "NULL output/workspace");
+    if (workspace_bytes < st_ksd_workspace_bytes(m, ld))
+        return fail(ST_ERR_INVALID, "workspace too small");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const st::PairArgs p{x, g, w, ld, d, l, tr, linv};
+    double* csum = static_cast<double*>(workspace);
+    rc = hip_check(st::launch_ksd_colsum(p, m, 0, m, csum, s),
+                   dense ? "dense ksd column-sum launch" : "ksd column-sum launch");
+    if (rc) return rc;
+    // the finish reads the diagonal only: k(x, x) depends on tr, not on L
+    return hip_check(st::launch_ksd_finish(p, m, csum, ks_out, s), "ksd finish launch");
+}
+
+int ksd_colsum(const double* x, const double* g, const double* w, int64_t n, int64_t ld, int32_t d, bool dense,
+               const double* linv, double l, double tr, int64_t row_begin, int64_t row_end, double* csum_out,
+               void* stream) {
+    int rc = check_problem(x, g, w, n, d, ld);
+    if (rc) return rc;
+    if (dense) rc = check_dense(linv, d);
+    if (rc) return rc;
+    if (!csum_out) return fail(ST_ERR_INVALID, "NULL output");
+    if (row_begin < 0 || row_end < row_begin || row_end > n)
+        return fail(ST_ERR_INVALID, "need 0 <= row_begin <= row_end <= n");
+    return hip_check(st::launch_ksd_colsum(st::PairArgs{x, g, w, ld, d, l, tr, linv}, n, row_begin, row_end,
+                                           csum_out, static_cast<hipStream_t>(stream)),
+                     dense ? "dense ksd column-sum launch" : "ksd column-sum launch");
+}
+
+int kmat(const double* x, const double* g, const double* w, int64_t k, int64_t ld, int32_t d, bool dense,
+         const double* linv, double l, double tr, double* kmat_out, void* stream) {
+    int rc = check_problem(x, g, w, k, d, ld);
+    if (rc) return rc;
+    if (dense) rc = check_dense(linv, d);
+    if (rc) return rc;
+    if (!kmat_out) return fail(ST_ERR_INVALID, "NULL output");
+    if ((k + 63) / 64 > 65535) return fail(ST_ERR_UNSUPPORTED, "k too large for the tiled grid");
+    return hip_check(st::launch_kmat(st::PairArgs{x, g, w, ld, d, l, tr, linv}, nullptr, k, kmat_out,
+                                     static_cast<hipStream_t>(stream)),
+                     dense ? "dense kmat launch" : "kmat launch");
+}
+
+// kernel densities: df = NULL for the Gaussian kernel, which tests d before the sizes (Student-t: after df)
+int kde_logpdf_grad(const double* p_soa, int64_t ldp, int64_t n, const double* log_weights,
+                    double log_weight_uniform, const double* q_soa, int64_t ldq, int64_t m, int32_t d,
+                    const double* df, double log_norm, const double* whiten, double* log_q_out, double* grad_out,
+                    void* workspace, int64_t workspace_bytes, void* stream) {
+    if (m == 0) return ST_OK;
+    if (!p_soa || !q_soa || !whiten || !log_q_out || !grad_out) return fail(ST_ERR_INVALID, "NULL pointer");
+    const bool bad_d = d < 1 || d > st::kMaxDim;
+    if (!df && bad_d) return fail(ST_ERR_UNSUPPORTED, "unsupported d = %d", d);
+    if (n < 1 || m < 0 || ldp < n || ldq < m) return fail(ST_ERR_INVALID, "bad sizes (need n >= 1, ld >= count)");
+    if (df && (!(*df > 0.0) || *df == INFINITY)) return fail(ST_ERR_INVALID, "df must be finite and > 0");
+    if (bad_d) return fail(ST_ERR_UNSUPPORTED, "unsupported d = %d", d);
+    if ((m + 255) / 256 > 0x7FFFFFFFll) return fail(ST_ERR_UNSUPPORTED, "m too large");
+    if (workspace_bytes < st::kde_workspace_bytes(m, d) || (st::kde_workspace_bytes(m, d) > 0 && !workspace))
+        return fail(ST_ERR_INVALID, "workspace too small (%lld < %lld)", (long long)workspace_bytes,
+                    (long long)st::kde_workspace_bytes(m, d));
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    double* ws = static_cast<double*>(workspace);
+    if (df)
+        return hip_check(st::launch_kde_t(p_soa, ldp, n, log_weights, log_weight_uniform, q_soa, ldq, m, d, *df,
+                                          log_norm, whiten, log_q_out, grad_out, ws, s),
+                         "kde_t launch");
+    return hip_check(st::launch_kde(p_soa, ldp, n, log_weights, log_weight_uniform, q_soa, ldq, m, d, log_norm,
+                                    whiten, log_q_out, grad_out, ws, s),
+                     "kde launch");
+}
+
+// accepted RK45 steps recorded per point by the two-phase gradient (typical: ~32 at the reference's
+// tolerances); a point that takes more is recomputed by the single-phase kernel
+constexpr int kLvStepCap = 64;
+
+// the part of their arguments that every LV entry point shares, checked and stored in one place; whiten
+// may be NULL where the kernels do not read U (the gradient)
+int lv_problem(st::LvProblem& p, const double* t_eval, int32_t t_n, const double* y_obs,
+               const double* span_u0_tol, const double* whiten, double c_log, double norm_logc,
+               int64_t max_steps, bool need_data) {
+    if (t_n < 1) return fail(ST_ERR_INVALID, "t_n must be >= 1");
+    if (!span_u0_tol) return fail(ST_ERR_INVALID, "NULL solver settings");
+    if (max_steps < 1) return fail(ST_ERR_INVALID, "max_steps must be >= 1");
+    if (need_data && (!t_eval || !y_obs)) return fail(ST_ERR_INVALID, "NULL pointer");
+    if (!(span_u0_tol[1] > span_u0_tol[0])) return fail(ST_ERR_INVALID, "need t1 > t0 (forward integration)");
+    if (!(span_u0_tol[4] > 0) || !(span_u0_tol[5] > 0)) return fail(ST_ERR_INVALID, "rtol and atol must be > 0");
+    p.t_eval = t_eval;
+    p.t_n = t_n;
+    p.y_obs = y_obs;
+    p.t0 = span_u0_tol[0];
+    p.t1 = span_u0_tol[1];
+    p.u0[0] = span_u0_tol[2];
+    p.u0[1] = span_u0_tol[3];
+    p.rtol = span_u0_tol[4];
+    p.atol = span_u0_tol[5];
+    for (int q = 0; q < 4 && whiten; ++q) p.U[q] = whiten[q];
+    p.c_log = c_log;
+    p.norm_logc = norm_logc;
+    p.max_steps = max_steps;
+    return ST_OK;
+}
+
+int lv_common(st::LvArgs& a, const double* theta, int64_t n, const double* t_eval, int32_t t_n,
+              const double* y_obs, const double* span_u0_tol, const double* whiten, double c_log,
+              double norm_logc, int64_t max_steps, double* out, int32_t* status) {
+    if (n < 0) return fail(ST_ERR_INVALID, "n must be >= 0");
+    int rc = lv_problem(a.p, t_eval, t_n, y_obs, span_u0_tol, whiten, c_log, norm_logc, max_steps, n > 0);
+    if (rc) return rc;
+    if (n > 0 && (!theta || !out || !status)) return fail(ST_ERR_INVALID, "NULL pointer");
+    a.theta = theta;
+    a.n = n;
+    a.out = out;
+    a.status = status;
+    return ST_OK;
+}
+
+// two_phase: with the step table in the caller's workspace (st_lv_grad_log_posterior_ws)
+int lv_grad(const double* theta, int64_t n, const double* t_eval, int32_t t_n, const double* y_obs,
+            const double* span_u0_tol, const double* cov_inv, int64_t max_steps, double* grad_out,
+            int32_t* status, bool two_phase, void* workspace, int64_t workspace_bytes, void* stream) {
+    st::LvArgs a{};
+    int rc = lv_common(a, theta, n, t_eval, t_n, y_obs, span_u0_tol, nullptr, 0.0, 0.0, max_steps, grad_out, status);
+    if (rc) return rc;
+    if (!cov_inv) return fail(ST_ERR_INVALID, "NULL cov_inv");
+    for (int q = 0; q < 4; ++q) a.cinv[q] = cov_inv[q];
+    if (two_phase) {
+        if (n > 0 && !workspace) return fail(ST_ERR_INVALID, "NULL workspace");
+        if (workspace_bytes < st::lv_grad_workspace_bytes(n, kLvStepCap))
+            return fail(ST_ERR_INVALID, "workspace too small");
+        a.step_cap = kLvStepCap;
+        a.steps = static_cast<double*>(workspace);
+        // the step counts follow the step table, whose bytes are what the capacity adds to the workspace
+        a.nsteps = reinterpret_cast<int32_t*>(static_cast<char*>(workspace) +
+                                              (st::lv_grad_workspace_bytes(n, kLvStepCap) -
+                                               st::lv_grad_workspace_bytes(n, 0)));
+    }
+    if (n == 0) return ST_OK;
+    return hip_check(st::launch_lv(a, true, static_cast<hipStream_t>(stream)), "lv gradient launch");
+}
+
+// the LV samplers' common checks (all before any HIP call) and the kernel arguments that LvMcmcArgs and
+// LvMalaArgs share, once; step_size: the random walk's step, MALA's eps (checked here, copied by the caller)
+template <class Args>
+int lv_rwmh_args(Args& a, double* state, int64_t chains, int64_t first_chain, int64_t first_step,
+                 int64_t steps, int32_t init, const double* step_size, int32_t noise_mode, uint64_t seed,
+                 double* z, double* log_u, int64_t noise_ld, int64_t noise_row0, const double* t_eval,
+                 int32_t t_n, const double* y_obs, const double* span_u0_tol, const double* whiten,
+                 double c_log, double norm_logc, int64_t max_steps, double* samples, double* log_p,
+                 int64_t out_ld, int64_t out_row0) {
+    if (chains < 1) return fail(ST_ERR_INVALID, "chains must be >= 1 (got %lld)", (long long)chains);
+    if (steps < 1) return fail(ST_ERR_INVALID, "steps must be >= 1 (got %lld)", (long long)steps);
+    int rc = lv_problem(a.p, t_eval, t_n, y_obs, span_u0_tol, whiten, c_log, norm_logc, max_steps, true);
+    if (rc) return rc;
+    if (first_step < 1) return fail(ST_ERR_INVALID, "first_step must be >= 1 (got %lld)", (long long)first_step);
+    if (first_chain < 0) return fail(ST_ERR_INVALID, "first_chain must be >= 0");
+    if (init != 0 && init != 1) return fail(ST_ERR_INVALID, "init must be 0 or 1");
+    if (noise_mode < 0 || noise_mode > 2) return fail(ST_ERR_INVALID, "noise_mode must be 0, 1 or 2");
+    if (!state || !samples || !log_p) return fail(ST_ERR_INVALID, "NULL pointer");
+    if (!step_size || !whiten) return fail(ST_ERR_INVALID, "NULL host settings");
+    if (noise_mode != 1) {
+        if (!z || !log_u)
+            return fail(ST_ERR_INVALID, "NULL noise arrays (z, log_u): noise_mode %d needs them", noise_mode);
+        if (noise_row0 < 0 || noise_ld < 1 || noise_row0 > noise_ld - steps)
+            return fail(ST_ERR_INVALID, "noise rows [%lld, %lld) outside the noise arrays' %lld rows",
+                        (long long)noise_row0, (long long)(noise_row0 + steps), (long long)noise_ld);
+        if (!aligned16(z) || !aligned8(log_u))
+            return fail(ST_ERR_INVALID, "noise arrays must be aligned (z: 16 bytes, log_u: 8)");
+    }
+    if (!aligned16(state) || !aligned16(samples))
+        return fail(ST_ERR_INVALID, "state and samples must be 16-byte aligned");
+    if (!aligned8(log_p) || !aligned8(t_eval) || !aligned8(y_obs))
+        return fail(ST_ERR_INVALID, "log_p, t_eval and y_obs must be 8-byte aligned");
+    if (out_ld < 1 || out_row0 < init || out_row0 > out_ld - steps)
+        return fail(ST_ERR_INVALID, "output rows [%lld, %lld) outside the output arrays' %lld rows",
+                    (long long)(out_row0 - init), (long long)(out_row0 + steps), (long long)out_ld);
+    if (init && first_step != 1) return fail(ST_ERR_INVALID, "init needs first_step = 1");
+    for (int j = 0; j < 4; ++j)
+        if (!isfinite(step_size[j]) || !(step_size[j] > 0))
+            return fail(ST_ERR_INVALID, "step size %d must be finite and > 0 (got %g)", j, step_size[j]);
+    a.state = state;
+    a.chains = chains;
+    a.first_chain = first_chain;
+    a.first_step = first_step;
+    a.steps = steps;
+    a.init = init;
+    a.noise_mode = noise_mode;
+    a.seed = seed;
+    a.z = z;
+    a.log_u = log_u;
+    a.noise_ld = noise_ld;
+    a.noise_row0 = noise_row0;
+    a.samples = samples;
+    a.log_p = log_p;
+    a.out_ld = out_ld;
+    a.out_row0 = out_row0;
+    return ST_OK;
+}
+
+// the random-walk sampler in either layout: launch = one chain per thread, or one wave per chain
+int lv_rwmh(hipError_t (*launch)(const st::LvMcmcArgs&, hipStream_t), const char* what, double* state,
+            int64_t chains, int64_t first_chain, int64_t first_step, int64_t steps, int32_t init,
+            const double* step_size, int32_t noise_mode, uint64_t seed, double* z, double* log_u, int64_t noise_ld,
+            int64_t noise_row0, const double* t_eval, int32_t t_n, const double* y_obs, const double* span_u0_tol,
+            const double* whiten, double c_log, double norm_logc, int64_t max_steps, double* samples,
+            double* log_p, int64_t out_ld, int64_t out_row0, void* stream) {
+    st::LvMcmcArgs a{};
+    int rc = lv_rwmh_args(a, state, chains, first_chain, first_step, steps, init, step_size, noise_mode, seed, z,
+                          log_u, noise_ld, noise_row0, t_eval, t_n, y_obs, span_u0_tol, whiten, c_log, norm_logc,
+                          max_steps, samples, log_p, out_ld, out_row0);
+    if (rc) return rc;
+    for (int j = 0; j < 4; ++j) a.step[j] = step_size[j];
+    return hip_check(launch(a, static_cast<hipStream_t>(stream)), what);
 }
 
 }  // namespace
@@ -99,25 +474,19 @@ int64_t st_greedy_workspace_bytes(int64_t n, int32_t d, int32_t nranks) {
 }
 
 int st_tune(int32_t key, int32_t value) {
-    int rc;
-    if (key == 7) rc = st::proxy_tune(value);
-    else if (key == 13) rc = st::dist_tune(value);
-    else if (key == 14) rc = st::dist_units_tune(value);
-    else if (key == 17) rc = st::lv_tune(value);
-    else if (key == 18) rc = st::lv_pieces_tune(value);
-    else if (key == 24) rc = st::kde_t_tune(value);
-    else rc = ((key >= 3 && key <= 5) || key == 8 || key == 9 || key == 10 || key == 12 || key == 15 || key == 16 ||
-               key == 19 || key == 23)
-                  ? st::persistent_tune(key, value)
-                  : st::tune(key, value);
+    const TuneKey k = tune_key(key);
+    const int rc = k.read_only                       ? -1
+                   : k.owner == TuneKey::kSetter     ? k.set(value)
+                   : k.owner == TuneKey::kPersistent ? st::persistent_tune(key, value)
+                                                     : st::tune(key, value);
     if (rc != 0) return fail(ST_ERR_INVALID, "bad tuning key/value %d=%d", key, value);
     return ST_OK;
 }
 
 int32_t st_tune_get(int32_t key) {
-    const bool persist = (key >= 3 && key <= 5) || key == 8 || key == 9 || key == 10 || key == 12 || key == 15 ||
-                         key == 16 || key == 19 || key == 23 || (key >= 100 && key <= 110);
-    return persist ? st::persistent_tune_get(key) : st::tune_get(key);
+    const TuneKey k = tune_key(key);
+    if (k.owner == TuneKey::kSetter) return INT32_MIN;   // write-only
+    return k.owner == TuneKey::kPersistent ? st::persistent_tune_get(key) : st::tune_get(key);
 }
 
 int64_t st_candidate_stride(int32_t d) {
@@ -134,34 +503,11 @@ int st_greedy_steps(const double* x_soa, const double* g_soa, const double* weig
     if (n_points < 1) return fail(ST_ERR_INVALID, "n_points must be >= 1");
     if (t_begin < 0 || t_end < t_begin || t_end > n_points)
         return fail(ST_ERR_INVALID, "need 0 <= t_begin <= t_end <= n_points");
-    if (!idx_out || !a_work || !workspace) return fail(ST_ERR_INVALID, "NULL output/workspace");
-    if (!aligned16(a_work) || !aligned16(workspace))
-        return fail(ST_ERR_INVALID, "a_work/workspace must be 16-byte aligned");
-    if (workspace_bytes < greedy_ws_bytes(d))
-        return fail(ST_ERR_INVALID, "workspace too small (%lld < %lld)", (long long)workspace_bytes,
-                    (long long)greedy_ws_bytes(d));
-    hipStream_t s = static_cast<hipStream_t>(stream);
+    rc = check_greedy_buffers("", idx_out, a_work, workspace, workspace_bytes, d);
+    if (rc) return rc;
     st::GreedyArgs a = make_args(x_soa, g_soa, weights, n, d, ld, linv_scale, linv_trace, a_work);
     a.idx_out = idx_out;
-    const int blocks = st::greedy_blocks(n, d);
-    if (t_begin == 0) {   // a run starts: no near-tie word of an earlier run may survive (step kernels: unguarded)
-        rc = hip_check(hipMemsetAsync(static_cast<char*>(workspace) + st::kWsTieOff, 0,
-                                      (size_t)(st::kWsBoundsOff + 40 - st::kWsTieOff), s),
-                       "near-tie words reset");
-        if (rc) return rc;
-    }
-    for (int64_t t = t_begin; t < t_end; ++t) {
-        a.t = t;
-        a.recs_in = bank(workspace, d, (int)((t + 1) & 1));
-        a.nrecs_in = blocks;
-        a.recs_out = bank(workspace, d, (int)(t & 1));
-        rc = hip_check(st::launch_greedy_step(a, t == 0, blocks, s), "greedy step launch");
-        if (rc) return rc;
-    }
-    if (t_end < n_points || t_end == t_begin) return ST_OK;
-    return hip_check(st::launch_greedy_finalize(bank(workspace, d, (int)((n_points - 1) & 1)), blocks,
-                                                a.rec_stride, idx_out, n_points - 1, s),
-                     "greedy finalize launch");
+    return run_steps(a, workspace, t_begin, t_end, n_points, static_cast<hipStream_t>(stream));
 }
 
 int st_greedy(const double* x_soa, const double* g_soa, const double* weights, int64_t n,
@@ -171,12 +517,8 @@ int st_greedy(const double* x_soa, const double* g_soa, const double* weights, i
     if (n_points < 1) return fail(ST_ERR_INVALID, "n_points must be >= 1");
     int rc = check_problem(x_soa, g_soa, weights, n, d, ld);
     if (rc) return rc;
-    if (!idx_out || !a_work || !workspace) return fail(ST_ERR_INVALID, "NULL output/workspace");
-    if (!aligned16(a_work) || !aligned16(workspace))
-        return fail(ST_ERR_INVALID, "a_work/workspace must be 16-byte aligned");
-    if (workspace_bytes < greedy_ws_bytes(d))
-        return fail(ST_ERR_INVALID, "workspace too small (%lld < %lld)", (long long)workspace_bytes,
-                    (long long)greedy_ws_bytes(d));
+    rc = check_greedy_buffers("", idx_out, a_work, workspace, workspace_bytes, d);
+    if (rc) return rc;
     int used = 0;
     const hipError_t pe = st::launch_greedy_persistent(
         x_soa, g_soa, weights, a_work, n, d, ld, linv_scale, linv_trace, n_points, idx_out, workspace,
@@ -196,35 +538,13 @@ int st_greedy_dense(const double* x_soa, const double* g_soa, const double* weig
     if (rc) return rc;
     rc = check_dense(linv, d);
     if (rc) return rc;
-    if (!idx_out || !a_work || !workspace) return fail(ST_ERR_INVALID, "NULL output/workspace");
-    if (!aligned16(a_work) || !aligned16(workspace))
-        return fail(ST_ERR_INVALID, "a_work/workspace must be 16-byte aligned");
-    if (workspace_bytes < greedy_ws_bytes(d))
-        return fail(ST_ERR_INVALID, "workspace too small (%lld < %lld)", (long long)workspace_bytes,
-                    (long long)greedy_ws_bytes(d));
-    hipStream_t s = static_cast<hipStream_t>(stream);
+    rc = check_greedy_buffers("", idx_out, a_work, workspace, workspace_bytes, d);
+    if (rc) return rc;
     st::GreedyArgs a = make_args(x_soa, g_soa, weights, n, d, ld, 0.0, linv_trace, a_work);
     a.compact = 0;   // one dense arithmetic; the diagonal is the exact one's
     a.linv = linv;
     a.idx_out = idx_out;
-    const int blocks = st::greedy_dense_blocks(n, d);
-    // a run starts: no near-tie word of an earlier run may survive (dense runs are unguarded: -2)
-    rc = hip_check(hipMemsetAsync(static_cast<char*>(workspace) + st::kWsTieOff, 0,
-                                  (size_t)(st::kWsBoundsOff + 40 - st::kWsTieOff), s),
-                   "near-tie words reset");
-    if (rc) return rc;
-    for (int64_t t = 0; t < n_points; ++t) {
-        a.t = t;
-        a.recs_in = bank(workspace, d, (int)((t + 1) & 1));
-        a.nrecs_in = blocks;
-        a.recs_out = bank(workspace, d, (int)(t & 1));
-        rc = hip_check(t == 0 ? st::launch_greedy_step(a, true, blocks, s) : st::launch_greedy_step_dense(a, blocks, s),
-                       "dense greedy step launch");
-        if (rc) return rc;
-    }
-    return hip_check(st::launch_greedy_finalize(bank(workspace, d, (int)((n_points - 1) & 1)), blocks,
-                                                a.rec_stride, idx_out, n_points - 1, s),
-                     "greedy finalize launch");
+    return run_steps(a, workspace, 0, n_points, n_points, static_cast<hipStream_t>(stream));
 }
 
 int st_greedy_near_tie(const void* workspace, int64_t workspace_bytes, int64_t* step_out, void* stream) {
@@ -267,13 +587,10 @@ int st_greedy_batch(int32_t count, const double* const* x_soa, const double* con
             return fail(ST_ERR_INVALID, "problem %d: weights must be given for every problem or none", q);
         int rc = check_problem(x_soa[q], g_soa[q], w, n[q], d, ld[q]);
         if (rc) return rc;
-        if (!idx_out[q] || !a_work[q] || !workspace[q])
-            return fail(ST_ERR_INVALID, "problem %d: NULL output/workspace", q);
-        if (!aligned16(a_work[q]) || !aligned16(workspace[q]))
-            return fail(ST_ERR_INVALID, "problem %d: a_work/workspace must be 16-byte aligned", q);
-        if (workspace_bytes[q] < greedy_ws_bytes(d))
-            return fail(ST_ERR_INVALID, "problem %d: workspace too small (%lld < %lld)", q,
-                        (long long)workspace_bytes[q], (long long)greedy_ws_bytes(d));
+        char who[24];
+        snprintf(who, sizeof(who), "problem %d: ", q);
+        rc = check_greedy_buffers(who, idx_out[q], a_work[q], workspace[q], workspace_bytes[q], d);
+        if (rc) return rc;
         pr[q] = st::BatchProblem{x_soa[q], g_soa[q], w, a_work[q], n[q], ld[q], linv_scale[q], linv_trace[q],
                                  idx_out[q], workspace[q], workspace_bytes[q]};
     }
@@ -338,25 +655,13 @@ int st_ipc_close_handle(void* dev_ptr) {
     return hip_check(hipIpcCloseMemHandle(dev_ptr), "hipIpcCloseMemHandle");
 }
 
-static int check_peers(void* const* peer_mailboxes, int32_t nranks, int32_t rank) {
-    if (nranks < 2 || nranks > st::kMailboxRanks)
-        return fail(ST_ERR_INVALID, "nranks must be in [2, %d]", st::kMailboxRanks);
-    if (rank < 0 || rank >= nranks) return fail(ST_ERR_INVALID, "rank out of range");
-    if (!peer_mailboxes) return fail(ST_ERR_INVALID, "NULL peer mailbox table");
-    for (int r = 0; r < nranks; ++r)
-        if (!peer_mailboxes[r] || !aligned16(peer_mailboxes[r]))
-            return fail(ST_ERR_INVALID, "peer mailbox %d is NULL or misaligned", r);
-    return ST_OK;
-}
-
 int st_mailbox_handshake(void* const* peer_mailboxes, int32_t nranks, int32_t rank,
                          uint64_t token, int32_t* ok_device, void* stream) {
     int rc = check_peers(peer_mailboxes, nranks, rank);
     if (rc) return rc;
     if (!ok_device) return fail(ST_ERR_INVALID, "NULL ok flag");
     if (token >> 63) return fail(ST_ERR_INVALID, "token must be < 2^63");
-    st::MailboxPeers peers{};
-    for (int r = 0; r < nranks; ++r) peers.p[r] = static_cast<uint64_t*>(peer_mailboxes[r]);
+    const st::MailboxPeers peers = mailbox_peers(peer_mailboxes, nranks);
     return hip_check(st::launch_mailbox_handshake(peers, peers.p[rank], rank, nranks,
                                                   token | (1ull << 63), ok_device,
                                                   static_cast<hipStream_t>(stream)),
@@ -376,20 +681,10 @@ int st_greedy_sharded(const double* x_soa, const double* g_soa, const double* we
     if (rc) return rc;
     if (row_begin < 0 || row_end <= row_begin || row_end > n)
         return fail(ST_ERR_INVALID, "need 0 <= row_begin < row_end <= n");
-    if (!idx_out || !a_work || !workspace) return fail(ST_ERR_INVALID, "NULL output/workspace");
-    if (!aligned16(a_work) || !aligned16(workspace))
-        return fail(ST_ERR_INVALID, "a_work/workspace must be 16-byte aligned");
-    if (workspace_bytes < greedy_ws_bytes(d))
-        return fail(ST_ERR_INVALID, "workspace too small (%lld < %lld)", (long long)workspace_bytes,
-                    (long long)greedy_ws_bytes(d));
-    st::RankSpec rs{};
-    rs.row_begin = row_begin;
-    rs.row_end = row_end;
-    rs.rank = rank;
-    rs.nranks = nranks;
-    rs.seq_base = seq_base;
-    rs.inbox = static_cast<uint64_t*>(peer_mailboxes[rank]);
-    for (int r = 0; r < nranks; ++r) rs.peer[r] = static_cast<uint64_t*>(peer_mailboxes[r]);
+    rc = check_greedy_buffers("", idx_out, a_work, workspace, workspace_bytes, d);
+    if (rc) return rc;
+    const st::RankSpec rs = rank_spec(row_begin, row_end, rank, nranks, seq_base, peer_mailboxes[rank],
+                                      peer_mailboxes);
     int used = 0;
     const hipError_t e = st::launch_greedy_persistent(
         x_soa, g_soa, weights, a_work, n, d, ld, linv_scale, linv_trace, n_points, idx_out, workspace,
@@ -413,12 +708,7 @@ int st_greedy_sharded_supported(int64_t n, int32_t d, int32_t has_weights, int64
     // the same decision st_greedy_sharded takes, without touching any buffer: placeholders for the
     // pointers, a non-null inbox, the workspace size the caller allocates (st_greedy_workspace_bytes)
     static uint64_t dummy_box[2];
-    st::RankSpec rs{};
-    rs.row_begin = row_begin;
-    rs.row_end = row_end;
-    rs.rank = rank;
-    rs.nranks = nranks;
-    rs.inbox = dummy_box;
+    const st::RankSpec rs = rank_spec(row_begin, row_end, rank, nranks, 0, dummy_box, nullptr);
     static double dummy_w;
     int used = 0;
     const hipError_t e = st::launch_greedy_persistent(
@@ -438,20 +728,15 @@ int st_greedy_step(const double* x_soa, const double* g_soa, const double* weigh
     if (t < 0) return fail(ST_ERR_INVALID, "t must be >= 0");
     if (nranks < 1 || nranks > 64) return fail(ST_ERR_INVALID, "nranks must be in [1, 64]");
     if (t > 0 && !cands_in) return fail(ST_ERR_INVALID, "cands_in is NULL for t > 0");
+    // the NULL test of check_greedy_buffers, early: it precedes the idx_out and row_offset checks (also below)
     if (!cand_out || !a_work || !workspace) return fail(ST_ERR_INVALID, "NULL output/workspace");
     if (t > 0 && !idx_out) return fail(ST_ERR_INVALID, "idx_out is NULL");
     if (row_offset < 0) return fail(ST_ERR_INVALID, "row_offset must be >= 0");
-    if (!aligned16(a_work) || !aligned16(workspace))
-        return fail(ST_ERR_INVALID, "a_work/workspace must be 16-byte aligned");
-    if (workspace_bytes < greedy_ws_bytes(d)) return fail(ST_ERR_INVALID, "workspace too small");
+    rc = check_greedy_buffers("", cand_out, a_work, workspace, workspace_bytes, d);
+    if (rc) return rc;
     hipStream_t s = static_cast<hipStream_t>(stream);
-    st::GreedyArgs a = make_args(x_soa, g_soa, weights, n, d, ld, linv_scale, linv_trace, a_work);
-    a.row_offset = row_offset;
-    a.t = t;
-    a.recs_in = cands_in;
-    a.nrecs_in = nranks;
-    a.recs_out = bank(workspace, d, 0);
-    a.idx_out = idx_out;
+    const st::GreedyArgs a = step_args(x_soa, g_soa, weights, n, d, ld, linv_scale, linv_trace, row_offset, t,
+                                       cands_in, nranks, idx_out, a_work, workspace);
     const int blocks = st::greedy_blocks(n, d);
     rc = hip_check(st::launch_greedy_step(a, t == 0, blocks, s), "greedy step launch");
     if (rc) return rc;
@@ -473,24 +758,17 @@ int st_greedy_step_exchange(const double* x_soa, const double* g_soa, const doub
     if (!cands || !a_work || !workspace || !status_device) return fail(ST_ERR_INVALID, "NULL output/workspace");
     if (t > 0 && !idx_out) return fail(ST_ERR_INVALID, "idx_out is NULL");
     if (row_offset < 0) return fail(ST_ERR_INVALID, "row_offset must be >= 0");
-    if (!aligned16(a_work) || !aligned16(workspace))
-        return fail(ST_ERR_INVALID, "a_work/workspace must be 16-byte aligned");
-    if (workspace_bytes < greedy_ws_bytes(d)) return fail(ST_ERR_INVALID, "workspace too small");
+    rc = check_greedy_buffers("", cands, a_work, workspace, workspace_bytes, d);
+    if (rc) return rc;
     hipStream_t s = static_cast<hipStream_t>(stream);
-    st::GreedyArgs a = make_args(x_soa, g_soa, weights, n, d, ld, linv_scale, linv_trace, a_work);
-    a.row_offset = row_offset;
-    a.t = t;
-    a.recs_in = cands;
-    a.nrecs_in = nranks;
-    a.recs_out = bank(workspace, d, 0);
-    a.idx_out = idx_out;
+    const st::GreedyArgs a = step_args(x_soa, g_soa, weights, n, d, ld, linv_scale, linv_trace, row_offset, t,
+                                       cands, nranks, idx_out, a_work, workspace);
     const int blocks = st::greedy_blocks(n, d);
     rc = hip_check(st::launch_greedy_step(a, t == 0, blocks, s), "greedy step launch");
     if (rc) return rc;
-    st::MailboxPeers peers{};
-    for (int r = 0; r < nranks; ++r) peers.p[r] = static_cast<uint64_t*>(peer_mailboxes[r]);
-    return hip_check(st::launch_greedy_rank_exchange(a.recs_out, blocks, a.rec_stride, d, peers, rank,
-                                                     nranks, t, cands, status_device, s),
+    return hip_check(st::launch_greedy_rank_exchange(a.recs_out, blocks, a.rec_stride, d,
+                                                     mailbox_peers(peer_mailboxes, nranks), rank, nranks, t,
+                                                     cands, status_device, s),
                      "rank exchange launch");
 }
 
@@ -503,18 +781,8 @@ int st_kde_logpdf_grad(const double* p_soa, int64_t ldp, int64_t n, const double
                        double log_weight_uniform, const double* q_soa, int64_t ldq, int64_t m, int32_t d,
                        double log_norm, const double* whiten, double* log_q_out, double* grad_out,
                        void* workspace, int64_t workspace_bytes, void* stream) {
-    if (m == 0) return ST_OK;
-    if (!p_soa || !q_soa || !whiten || !log_q_out || !grad_out) return fail(ST_ERR_INVALID, "NULL pointer");
-    if (d < 1 || d > st::kMaxDim) return fail(ST_ERR_UNSUPPORTED, "unsupported d = %d", d);
-    if (n < 1 || m < 0 || ldp < n || ldq < m) return fail(ST_ERR_INVALID, "bad sizes (need n >= 1, ld >= count)");
-    if ((m + 255) / 256 > 0x7FFFFFFFll) return fail(ST_ERR_UNSUPPORTED, "m too large");
-    if (workspace_bytes < st::kde_workspace_bytes(m, d) || (st::kde_workspace_bytes(m, d) > 0 && !workspace))
-        return fail(ST_ERR_INVALID, "workspace too small (%lld < %lld)", (long long)workspace_bytes,
-                    (long long)st::kde_workspace_bytes(m, d));
-    return hip_check(st::launch_kde(p_soa, ldp, n, log_weights, log_weight_uniform, q_soa, ldq, m, d, log_norm,
-                                    whiten, log_q_out, grad_out, static_cast<double*>(workspace),
-                                    static_cast<hipStream_t>(stream)),
-                     "kde launch");
+    return kde_logpdf_grad(p_soa, ldp, n, log_weights, log_weight_uniform, q_soa, ldq, m, d, nullptr, log_norm,
+                           whiten, log_q_out, grad_out, workspace, workspace_bytes, stream);
 }
 
 int64_t st_kde_t_workspace_bytes(int64_t m, int32_t d) {
@@ -526,19 +794,8 @@ int st_kde_t_logpdf_grad(const double* p_soa, int64_t ldp, int64_t n, const doub
                          double log_weight_uniform, const double* q_soa, int64_t ldq, int64_t m, int32_t d,
                          double df, double log_norm, const double* whiten, double* log_q_out, double* grad_out,
                          void* workspace, int64_t workspace_bytes, void* stream) {
-    if (m == 0) return ST_OK;
-    if (!p_soa || !q_soa || !whiten || !log_q_out || !grad_out) return fail(ST_ERR_INVALID, "NULL pointer");
-    if (n < 1 || m < 0 || ldp < n || ldq < m) return fail(ST_ERR_INVALID, "bad sizes (need n >= 1, ld >= count)");
-    if (!(df > 0.0) || df == INFINITY) return fail(ST_ERR_INVALID, "df must be finite and > 0");
-    if (d < 1 || d > st::kMaxDim) return fail(ST_ERR_UNSUPPORTED, "unsupported d = %d", d);
-    if ((m + 255) / 256 > 0x7FFFFFFFll) return fail(ST_ERR_UNSUPPORTED, "m too large");
-    if (workspace_bytes < st::kde_workspace_bytes(m, d) || (st::kde_workspace_bytes(m, d) > 0 && !workspace))
-        return fail(ST_ERR_INVALID, "workspace too small (%lld < %lld)", (long long)workspace_bytes,
-                    (long long)st::kde_workspace_bytes(m, d));
-    return hip_check(st::launch_kde_t(p_soa, ldp, n, log_weights, log_weight_uniform, q_soa, ldq, m, d, df,
-                                      log_norm, whiten, log_q_out, grad_out, static_cast<double*>(workspace),
-                                      static_cast<hipStream_t>(stream)),
-                     "kde_t launch");
+    return kde_logpdf_grad(p_soa, ldp, n, log_weights, log_weight_uniform, q_soa, ldq, m, d, &df, log_norm,
+                           whiten, log_q_out, grad_out, workspace, workspace_bytes, stream);
 }
 
 int st_proxy_logpdf_grad(const double* x, int64_t n, int32_t d, const double* loc,
@@ -563,10 +820,9 @@ int st_mixture_logpdf_score(const double* x, int64_t n, int32_t d, int32_t k, co
     if (k < 1) return fail(ST_ERR_INVALID, "k must be >= 1 (got %d)", k);
     if (!log_coef || !means || !precision || (n > 0 && (!x || !log_p_out || !score_out)))
         return fail(ST_ERR_INVALID, "NULL pointer");
-    const uintptr_t bits = reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(log_coef) |
-                           reinterpret_cast<uintptr_t>(means) | reinterpret_cast<uintptr_t>(precision) |
-                           reinterpret_cast<uintptr_t>(log_p_out) | reinterpret_cast<uintptr_t>(score_out);
-    if (bits & 7u) return fail(ST_ERR_INVALID, "device arrays must be 8-byte aligned");
+    if (!aligned8(x) || !aligned8(log_coef) || !aligned8(means) || !aligned8(precision) || !aligned8(log_p_out) ||
+        !aligned8(score_out))
+        return fail(ST_ERR_INVALID, "device arrays must be 8-byte aligned");
     if (d > st::kMixtureMaxDim)
         return fail(ST_ERR_UNSUPPORTED, "d = %d exceeds the mixture kernels' maximum %d", d, st::kMixtureMaxDim);
     if (k > st::kMixtureMaxComponents)
@@ -587,10 +843,8 @@ int st_mvt_moments(const double* x, int64_t n, int32_t d, const double* loc, con
     if (d < 1) return fail(ST_ERR_INVALID, "d must be >= 1 (got %d)", d);
     if (!(df > 0.0) || df == INFINITY) return fail(ST_ERR_INVALID, "df must be finite and > 0");
     if (!x || !loc || !whiten || !out || !workspace) return fail(ST_ERR_INVALID, "NULL pointer");
-    const uintptr_t bits = reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(loc) |
-                           reinterpret_cast<uintptr_t>(whiten) | reinterpret_cast<uintptr_t>(out) |
-                           reinterpret_cast<uintptr_t>(workspace);
-    if (bits & 7u) return fail(ST_ERR_INVALID, "device arrays must be 8-byte aligned");
+    if (!aligned8(x) || !aligned8(loc) || !aligned8(whiten) || !aligned8(out) || !aligned8(workspace))
+        return fail(ST_ERR_INVALID, "device arrays must be 8-byte aligned");
     if (d > st::kMvtMaxDim)
         return fail(ST_ERR_UNSUPPORTED, "d = %d exceeds the moment kernels' maximum %d", d, st::kMvtMaxDim);
     if (workspace_bytes < st::mvt_moments_ws_bytes(n, d))
@@ -600,61 +854,11 @@ int st_mvt_moments(const double* x, int64_t n, int32_t d, const double* loc, con
     return hip_check(st::launch_mvt_moments(a, static_cast<hipStream_t>(stream)), "mvt moments launch");
 }
 
-// accepted RK45 steps recorded per point by the two-phase gradient (typical: ~32 at the reference's
-// tolerances); a point that takes more is recomputed by the single-phase kernel
-constexpr int kLvStepCap = 64;
-
-// the part of their arguments that every LV entry point shares, checked and stored in one place; whiten
-// may be NULL where the kernels do not read U (the gradient)
-static int lv_problem(st::LvProblem& p, const double* t_eval, int32_t t_n, const double* y_obs,
-                      const double* span_u0_tol, const double* whiten, double c_log, double norm_logc,
-                      int64_t max_steps, bool need_data) {
-    if (t_n < 1) return fail(ST_ERR_INVALID, "t_n must be >= 1");
-    if (!span_u0_tol) return fail(ST_ERR_INVALID, "NULL solver settings");
-    if (max_steps < 1) return fail(ST_ERR_INVALID, "max_steps must be >= 1");
-    if (need_data && (!t_eval || !y_obs)) return fail(ST_ERR_INVALID, "NULL pointer");
-    if (!(span_u0_tol[1] > span_u0_tol[0])) return fail(ST_ERR_INVALID, "need t1 > t0 (forward integration)");
-    if (!(span_u0_tol[4] > 0) || !(span_u0_tol[5] > 0)) return fail(ST_ERR_INVALID, "rtol and atol must be > 0");
-    p.t_eval = t_eval;
-    p.t_n = t_n;
-    p.y_obs = y_obs;
-    p.t0 = span_u0_tol[0];
-    p.t1 = span_u0_tol[1];
-    p.u0[0] = span_u0_tol[2];
-    p.u0[1] = span_u0_tol[3];
-    p.rtol = span_u0_tol[4];
-    p.atol = span_u0_tol[5];
-    for (int q = 0; q < 4 && whiten; ++q) p.U[q] = whiten[q];
-    p.c_log = c_log;
-    p.norm_logc = norm_logc;
-    p.max_steps = max_steps;
-    return ST_OK;
-}
-
-static int lv_common(st::LvArgs& a, const double* theta, int64_t n, const double* t_eval, int32_t t_n,
-                     const double* y_obs, const double* span_u0_tol, const double* whiten, double c_log,
-                     double norm_logc, int64_t max_steps, double* out, int32_t* status) {
-    if (n < 0) return fail(ST_ERR_INVALID, "n must be >= 0");
-    int rc = lv_problem(a.p, t_eval, t_n, y_obs, span_u0_tol, whiten, c_log, norm_logc, max_steps, n > 0);
-    if (rc) return rc;
-    if (n > 0 && (!theta || !out || !status)) return fail(ST_ERR_INVALID, "NULL pointer");
-    a.theta = theta;
-    a.n = n;
-    a.out = out;
-    a.status = status;
-    return ST_OK;
-}
-
 int st_lv_grad_log_posterior(const double* theta, int64_t n, const double* t_eval, int32_t t_n,
                              const double* y_obs, const double* span_u0_tol, const double* cov_inv,
                              int64_t max_steps, double* grad_out, int32_t* status, void* stream) {
-    st::LvArgs a{};
-    int rc = lv_common(a, theta, n, t_eval, t_n, y_obs, span_u0_tol, nullptr, 0.0, 0.0, max_steps, grad_out, status);
-    if (rc) return rc;
-    if (!cov_inv) return fail(ST_ERR_INVALID, "NULL cov_inv");
-    for (int q = 0; q < 4; ++q) a.cinv[q] = cov_inv[q];
-    if (n == 0) return ST_OK;
-    return hip_check(st::launch_lv(a, true, static_cast<hipStream_t>(stream)), "lv gradient launch");
+    return lv_grad(theta, n, t_eval, t_n, y_obs, span_u0_tol, cov_inv, max_steps, grad_out, status, false, nullptr,
+                   0, stream);
 }
 
 int64_t st_lv_grad_workspace_bytes(int64_t n, int32_t t_n) {
@@ -666,18 +870,8 @@ int st_lv_grad_log_posterior_ws(const double* theta, int64_t n, const double* t_
                                 const double* y_obs, const double* span_u0_tol, const double* cov_inv,
                                 int64_t max_steps, double* grad_out, int32_t* status, void* workspace,
                                 int64_t workspace_bytes, void* stream) {
-    st::LvArgs a{};
-    int rc = lv_common(a, theta, n, t_eval, t_n, y_obs, span_u0_tol, nullptr, 0.0, 0.0, max_steps, grad_out, status);
-    if (rc) return rc;
-    if (!cov_inv) return fail(ST_ERR_INVALID, "NULL cov_inv");
-    if (n > 0 && !workspace) return fail(ST_ERR_INVALID, "NULL workspace");
-    if (workspace_bytes < st::lv_grad_workspace_bytes(n, kLvStepCap)) return fail(ST_ERR_INVALID, "workspace too small");
-    for (int q = 0; q < 4; ++q) a.cinv[q] = cov_inv[q];
-    a.step_cap = kLvStepCap;
-    a.steps = static_cast<double*>(workspace);
-    a.nsteps = reinterpret_cast<int32_t*>(static_cast<char*>(workspace) + n * (int64_t)kLvStepCap * 56 * 8);
-    if (n == 0) return ST_OK;
-    return hip_check(st::launch_lv(a, true, static_cast<hipStream_t>(stream)), "lv gradient launch");
+    return lv_grad(theta, n, t_eval, t_n, y_obs, span_u0_tol, cov_inv, max_steps, grad_out, status, true, workspace,
+                   workspace_bytes, stream);
 }
 
 int64_t st_lv_log_density_workspace_bytes(int64_t n, int32_t t_n) {
@@ -707,80 +901,15 @@ int64_t st_lv_rwmh_workspace_bytes(int64_t chains) {
     return chains * 64;
 }
 
-// the LV samplers' common checks (all before any HIP call) and the kernel arguments that LvMcmcArgs and
-// LvMalaArgs share, once; step_size: the random walk's step, MALA's eps (checked here, copied by the caller)
-extern "C++" {
-template <class Args>
-static int lv_rwmh_args(Args& a, double* state, int64_t chains, int64_t first_chain, int64_t first_step,
-                        int64_t steps, int32_t init, const double* step_size, int32_t noise_mode, uint64_t seed,
-                        double* z, double* log_u, int64_t noise_ld, int64_t noise_row0, const double* t_eval,
-                        int32_t t_n, const double* y_obs, const double* span_u0_tol, const double* whiten,
-                        double c_log, double norm_logc, int64_t max_steps, double* samples, double* log_p,
-                        int64_t out_ld, int64_t out_row0) {
-    if (chains < 1) return fail(ST_ERR_INVALID, "chains must be >= 1 (got %lld)", (long long)chains);
-    if (steps < 1) return fail(ST_ERR_INVALID, "steps must be >= 1 (got %lld)", (long long)steps);
-    int rc = lv_problem(a.p, t_eval, t_n, y_obs, span_u0_tol, whiten, c_log, norm_logc, max_steps, true);
-    if (rc) return rc;
-    if (first_step < 1) return fail(ST_ERR_INVALID, "first_step must be >= 1 (got %lld)", (long long)first_step);
-    if (first_chain < 0) return fail(ST_ERR_INVALID, "first_chain must be >= 0");
-    if (init != 0 && init != 1) return fail(ST_ERR_INVALID, "init must be 0 or 1");
-    if (noise_mode < 0 || noise_mode > 2) return fail(ST_ERR_INVALID, "noise_mode must be 0, 1 or 2");
-    if (!state || !samples || !log_p) return fail(ST_ERR_INVALID, "NULL pointer");
-    if (!step_size || !whiten) return fail(ST_ERR_INVALID, "NULL host settings");
-    if (noise_mode != 1) {
-        if (!z || !log_u)
-            return fail(ST_ERR_INVALID, "NULL noise arrays (z, log_u): noise_mode %d needs them", noise_mode);
-        if (noise_row0 < 0 || noise_ld < 1 || noise_row0 > noise_ld - steps)
-            return fail(ST_ERR_INVALID, "noise rows [%lld, %lld) outside the noise arrays' %lld rows",
-                        (long long)noise_row0, (long long)(noise_row0 + steps), (long long)noise_ld);
-        if (!aligned16(z) || (reinterpret_cast<uintptr_t>(log_u) & 7u))
-            return fail(ST_ERR_INVALID, "noise arrays must be aligned (z: 16 bytes, log_u: 8)");
-    }
-    if (!aligned16(state) || !aligned16(samples))
-        return fail(ST_ERR_INVALID, "state and samples must be 16-byte aligned");
-    if ((reinterpret_cast<uintptr_t>(log_p) & 7u) || (reinterpret_cast<uintptr_t>(t_eval) & 7u) ||
-        (reinterpret_cast<uintptr_t>(y_obs) & 7u))
-        return fail(ST_ERR_INVALID, "log_p, t_eval and y_obs must be 8-byte aligned");
-    if (out_ld < 1 || out_row0 < init || out_row0 > out_ld - steps)
-        return fail(ST_ERR_INVALID, "output rows [%lld, %lld) outside the output arrays' %lld rows",
-                    (long long)(out_row0 - init), (long long)(out_row0 + steps), (long long)out_ld);
-    if (init && first_step != 1) return fail(ST_ERR_INVALID, "init needs first_step = 1");
-    for (int j = 0; j < 4; ++j)
-        if (!isfinite(step_size[j]) || !(step_size[j] > 0))
-            return fail(ST_ERR_INVALID, "step size %d must be finite and > 0 (got %g)", j, step_size[j]);
-    a.state = state;
-    a.chains = chains;
-    a.first_chain = first_chain;
-    a.first_step = first_step;
-    a.steps = steps;
-    a.init = init;
-    a.noise_mode = noise_mode;
-    a.seed = seed;
-    a.z = z;
-    a.log_u = log_u;
-    a.noise_ld = noise_ld;
-    a.noise_row0 = noise_row0;
-    a.samples = samples;
-    a.log_p = log_p;
-    a.out_ld = out_ld;
-    a.out_row0 = out_row0;
-    return ST_OK;
-}
-}  // extern "C++"
-
 int st_lv_rwmh(double* state, int64_t chains, int64_t first_chain, int64_t first_step, int64_t steps,
                int32_t init, const double* step_size, int32_t noise_mode, uint64_t seed, double* z,
                double* log_u, int64_t noise_ld, int64_t noise_row0, const double* t_eval, int32_t t_n,
                const double* y_obs, const double* span_u0_tol, const double* whiten, double c_log,
                double norm_logc, int64_t max_steps, double* samples, double* log_p, int64_t out_ld,
                int64_t out_row0, void* stream) {
-    st::LvMcmcArgs a{};
-    int rc = lv_rwmh_args(a, state, chains, first_chain, first_step, steps, init, step_size, noise_mode, seed, z,
-                          log_u, noise_ld, noise_row0, t_eval, t_n, y_obs, span_u0_tol, whiten, c_log, norm_logc,
-                          max_steps, samples, log_p, out_ld, out_row0);
-    if (rc) return rc;
-    for (int j = 0; j < 4; ++j) a.step[j] = step_size[j];
-    return hip_check(st::launch_lv_rwmh(a, static_cast<hipStream_t>(stream)), "lv rwmh launch");
+    return lv_rwmh(st::launch_lv_rwmh, "lv rwmh launch", state, chains, first_chain, first_step, steps, init,
+                   step_size, noise_mode, seed, z, log_u, noise_ld, noise_row0, t_eval, t_n, y_obs, span_u0_tol,
+                   whiten, c_log, norm_logc, max_steps, samples, log_p, out_ld, out_row0, stream);
 }
 
 int st_lv_rwmh_wave(double* state, int64_t chains, int64_t first_chain, int64_t first_step, int64_t steps,
@@ -789,13 +918,9 @@ int st_lv_rwmh_wave(double* state, int64_t chains, int64_t first_chain, int64_t 
                     const double* y_obs, const double* span_u0_tol, const double* whiten, double c_log,
                     double norm_logc, int64_t max_steps, double* samples, double* log_p, int64_t out_ld,
                     int64_t out_row0, void* stream) {
-    st::LvMcmcArgs a{};
-    int rc = lv_rwmh_args(a, state, chains, first_chain, first_step, steps, init, step_size, noise_mode, seed, z,
-                          log_u, noise_ld, noise_row0, t_eval, t_n, y_obs, span_u0_tol, whiten, c_log, norm_logc,
-                          max_steps, samples, log_p, out_ld, out_row0);
-    if (rc) return rc;
-    for (int j = 0; j < 4; ++j) a.step[j] = step_size[j];
-    return hip_check(st::launch_lv_rwmh_wave(a, static_cast<hipStream_t>(stream)), "lv rwmh wave launch");
+    return lv_rwmh(st::launch_lv_rwmh_wave, "lv rwmh wave launch", state, chains, first_chain, first_step, steps,
+                   init, step_size, noise_mode, seed, z, log_u, noise_ld, noise_row0, t_eval, t_n, y_obs,
+                   span_u0_tol, whiten, c_log, norm_logc, max_steps, samples, log_p, out_ld, out_row0, stream);
 }
 
 int64_t st_lv_mala_workspace_bytes(int64_t chains) {
@@ -849,14 +974,8 @@ int st_greedy_finalize(const double* cands_in, int32_t nranks, int32_t d, uint32
 int st_kernel_pairs(const double* x_soa, const double* g_soa, const double* weights, int64_t ld,
                     int32_t d, double linv_scale, double linv_trace, const int64_t* i1,
                     const int64_t* i2, int64_t n_pairs, double* out, void* stream) {
-    if (n_pairs == 0) return ST_OK;
-    if (!x_soa || !g_soa) return fail(ST_ERR_INVALID, "sample/gradient pointer is NULL");
-    if (d < 1 || d > st::kMaxDim) return fail(ST_ERR_UNSUPPORTED, "unsupported d = %d", d);
-    if (ld < 1) return fail(ST_ERR_INVALID, "ld must be >= 1");
-    if (n_pairs < 0 || !i1 || !i2 || !out) return fail(ST_ERR_INVALID, "bad pair list");
-    st::PairArgs p{x_soa, g_soa, weights, ld, d, linv_scale, linv_trace};
-    return hip_check(st::launch_pairs(p, i1, i2, n_pairs, out, static_cast<hipStream_t>(stream)),
-                     "pairs launch");
+    return kernel_pairs(x_soa, g_soa, weights, ld, d, false, nullptr, linv_scale, linv_trace, i1, i2, n_pairs, out,
+                        stream);
 }
 
 int64_t st_ksd_workspace_bytes(int64_t m, int64_t ld) {
@@ -867,31 +986,15 @@ int64_t st_ksd_workspace_bytes(int64_t m, int64_t ld) {
 int st_ksd_cumulative(const double* x_soa, const double* g_soa, const double* weights, int64_t m,
                       int64_t ld, int32_t d, double linv_scale, double linv_trace, double* ks_out,
                       void* workspace, int64_t workspace_bytes, void* stream) {
-    int rc = check_problem(x_soa, g_soa, weights, m, d, ld);
-    if (rc) return rc;
-    if (!ks_out || !workspace) return fail(ST_ERR_INVALID, "NULL output/workspace");
-    if (workspace_bytes < st_ksd_workspace_bytes(m, ld))
-        return fail(ST_ERR_INVALID, "workspace too small");
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    st::PairArgs p{x_soa, g_soa, weights, ld, d, linv_scale, linv_trace};
-    double* csum = static_cast<double*>(workspace);
-    rc = hip_check(st::launch_ksd_colsum(p, m, 0, m, csum, s), "ksd column-sum launch");
-    if (rc) return rc;
-    return hip_check(st::launch_ksd_finish(p, m, csum, ks_out, s), "ksd finish launch");
+    return ksd_cumulative(x_soa, g_soa, weights, m, ld, d, false, nullptr, linv_scale, linv_trace, ks_out,
+                          workspace, workspace_bytes, stream);
 }
 
 int st_ksd_colsum(const double* x_soa, const double* g_soa, const double* weights, int64_t n,
                   int64_t ld, int32_t d, double linv_scale, double linv_trace, int64_t row_begin,
                   int64_t row_end, double* csum_out, void* stream) {
-    int rc = check_problem(x_soa, g_soa, weights, n, d, ld);
-    if (rc) return rc;
-    if (!csum_out) return fail(ST_ERR_INVALID, "NULL output");
-    if (row_begin < 0 || row_end < row_begin || row_end > n)
-        return fail(ST_ERR_INVALID, "need 0 <= row_begin <= row_end <= n");
-    st::PairArgs p{x_soa, g_soa, weights, ld, d, linv_scale, linv_trace};
-    return hip_check(st::launch_ksd_colsum(p, n, row_begin, row_end, csum_out,
-                                           static_cast<hipStream_t>(stream)),
-                     "ksd column-sum launch");
+    return ksd_colsum(x_soa, g_soa, weights, n, ld, d, false, nullptr, linv_scale, linv_trace, row_begin, row_end,
+                      csum_out, stream);
 }
 
 int st_ksd_finish(const double* x_soa, const double* g_soa, const double* weights, int64_t n,
@@ -941,23 +1044,6 @@ int st_distance_colsum_ws(const double* a_soa, int64_t lda, int64_t na, const do
 }
 
 // ---- set-batched forms: one resident problem, many index sets (csrc/sets.hpp) ----------------------
-static bool aligned8(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 7u) == 0; }
-
-// the checks both entry points share, after the problem's own: rows, offsets, sizes
-static int check_sets(const int64_t* rows, const int64_t* set_offsets, int64_t n_sets) {
-    if (!rows || !set_offsets) return fail(ST_ERR_INVALID, "rows/set_offsets pointer is NULL");
-    if (!aligned8(rows) || !aligned8(set_offsets)) return fail(ST_ERR_INVALID, "rows/set_offsets must be 8-byte aligned");
-    switch (st::sets_check_offsets(set_offsets, n_sets)) {
-        case 1: return fail(ST_ERR_INVALID, "set_offsets[0] must be 0 (got %lld)", (long long)set_offsets[0]);
-        case 2: return fail(ST_ERR_INVALID, "set_offsets must not decrease");
-        case 3: return fail(ST_ERR_INVALID, "empty index set");
-        default: break;
-    }
-    if (n_sets > 0x7FFFFFFFll || st::sets_item_count(set_offsets, n_sets) > 0x7FFFFFFFll)
-        return fail(ST_ERR_UNSUPPORTED, "too many sets / column blocks for one grid");
-    return ST_OK;
-}
-
 int64_t st_sets_work_items(const int64_t* set_offsets, int64_t n_sets, int32_t* items_out, int64_t capacity) {
     if (!set_offsets || n_sets < 0 || !aligned8(set_offsets)) return -1;
     if (n_sets == 0) return 0;
@@ -1029,76 +1115,32 @@ int st_distance_sets(const double* p_soa, int64_t ldp, int64_t n, int32_t d, con
 
 int st_kmat(const double* x_soa, const double* g_soa, const double* weights, int64_t k, int64_t ld,
             int32_t d, double linv_scale, double linv_trace, double* kmat_out, void* stream) {
-    int rc = check_problem(x_soa, g_soa, weights, k, d, ld);
-    if (rc) return rc;
-    if (!kmat_out) return fail(ST_ERR_INVALID, "NULL output");
-    if ((k + 63) / 64 > 65535) return fail(ST_ERR_UNSUPPORTED, "k too large for the tiled grid");
-    st::PairArgs p{x_soa, g_soa, weights, ld, d, linv_scale, linv_trace};
-    return hip_check(st::launch_kmat(p, nullptr, k, kmat_out, static_cast<hipStream_t>(stream)),
-                     "kmat launch");
+    return kmat(x_soa, g_soa, weights, k, ld, d, false, nullptr, linv_scale, linv_trace, kmat_out, stream);
 }
 
 int st_kernel_pairs_dense(const double* x_soa, const double* g_soa, const double* weights, int64_t ld,
                           int32_t d, const double* linv, double linv_trace, const int64_t* i1,
                           const int64_t* i2, int64_t n_pairs, double* out, void* stream) {
-    if (n_pairs == 0) return ST_OK;
-    if (!x_soa || !g_soa) return fail(ST_ERR_INVALID, "sample/gradient pointer is NULL");
-    if (d < 1) return fail(ST_ERR_INVALID, "d must be >= 1 (got %d)", d);
-    int rc = check_dense(linv, d);
-    if (rc) return rc;
-    if (ld < 1) return fail(ST_ERR_INVALID, "ld must be >= 1");
-    if (n_pairs < 0 || !i1 || !i2 || !out) return fail(ST_ERR_INVALID, "bad pair list");
-    st::PairArgs p{x_soa, g_soa, weights, ld, d, 0.0, linv_trace, linv};
-    return hip_check(st::launch_pairs(p, i1, i2, n_pairs, out, static_cast<hipStream_t>(stream)),
-                     "dense pairs launch");
+    return kernel_pairs(x_soa, g_soa, weights, ld, d, true, linv, 0.0, linv_trace, i1, i2, n_pairs, out, stream);
 }
 
 int st_ksd_colsum_dense(const double* x_soa, const double* g_soa, const double* weights, int64_t n,
                         int64_t ld, int32_t d, const double* linv, double linv_trace, int64_t row_begin,
                         int64_t row_end, double* csum_out, void* stream) {
-    int rc = check_problem(x_soa, g_soa, weights, n, d, ld);
-    if (rc) return rc;
-    rc = check_dense(linv, d);
-    if (rc) return rc;
-    if (!csum_out) return fail(ST_ERR_INVALID, "NULL output");
-    if (row_begin < 0 || row_end < row_begin || row_end > n)
-        return fail(ST_ERR_INVALID, "need 0 <= row_begin <= row_end <= n");
-    st::PairArgs p{x_soa, g_soa, weights, ld, d, 0.0, linv_trace, linv};
-    return hip_check(st::launch_ksd_colsum(p, n, row_begin, row_end, csum_out,
-                                           static_cast<hipStream_t>(stream)),
-                     "dense ksd column-sum launch");
+    return ksd_colsum(x_soa, g_soa, weights, n, ld, d, true, linv, 0.0, linv_trace, row_begin, row_end, csum_out,
+                      stream);
 }
 
 int st_ksd_cumulative_dense(const double* x_soa, const double* g_soa, const double* weights, int64_t m,
                             int64_t ld, int32_t d, const double* linv, double linv_trace, double* ks_out,
                             void* workspace, int64_t workspace_bytes, void* stream) {
-    int rc = check_problem(x_soa, g_soa, weights, m, d, ld);
-    if (rc) return rc;
-    rc = check_dense(linv, d);
-    if (rc) return rc;
-    if (!ks_out || !workspace) return fail(ST_ERR_INVALID, "NULL output/workspace");
-    if (workspace_bytes < st_ksd_workspace_bytes(m, ld))
-        return fail(ST_ERR_INVALID, "workspace too small");
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    st::PairArgs p{x_soa, g_soa, weights, ld, d, 0.0, linv_trace, linv};
-    double* csum = static_cast<double*>(workspace);
-    rc = hip_check(st::launch_ksd_colsum(p, m, 0, m, csum, s), "dense ksd column-sum launch");
-    if (rc) return rc;
-    // the finish reads the diagonal only: k(x, x) depends on tr, not on L
-    return hip_check(st::launch_ksd_finish(p, m, csum, ks_out, s), "ksd finish launch");
+    return ksd_cumulative(x_soa, g_soa, weights, m, ld, d, true, linv, 0.0, linv_trace, ks_out, workspace,
+                          workspace_bytes, stream);
 }
 
 int st_kmat_dense(const double* x_soa, const double* g_soa, const double* weights, int64_t k, int64_t ld,
                   int32_t d, const double* linv, double linv_trace, double* kmat_out, void* stream) {
-    int rc = check_problem(x_soa, g_soa, weights, k, d, ld);
-    if (rc) return rc;
-    rc = check_dense(linv, d);
-    if (rc) return rc;
-    if (!kmat_out) return fail(ST_ERR_INVALID, "NULL output");
-    if ((k + 63) / 64 > 65535) return fail(ST_ERR_UNSUPPORTED, "k too large for the tiled grid");
-    st::PairArgs p{x_soa, g_soa, weights, ld, d, 0.0, linv_trace, linv};
-    return hip_check(st::launch_kmat(p, nullptr, k, kmat_out, static_cast<hipStream_t>(stream)),
-                     "dense kmat launch");
+    return kmat(x_soa, g_soa, weights, k, ld, d, true, linv, 0.0, linv_trace, kmat_out, stream);
 }
 
 int st_layout_soa(const double* rowmajor, int64_t n, int32_t d, int64_t ld, double* soa,
