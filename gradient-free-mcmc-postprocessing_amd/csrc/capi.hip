@@ -960,6 +960,39 @@ int st_lv_mala_wave(double* state, int64_t chains, int64_t first_chain, int64_t 
     return hip_check(st::launch_lv_mala_wave(a, static_cast<hipStream_t>(stream)), "lv mala wave launch");
 }
 
+int64_t st_lv_hmc_workspace_bytes(int64_t chains) {
+    if (chains < 1) return -1;
+    return chains * 128;
+}
+
+int st_lv_hmc_wave(double* state, int64_t chains, int64_t first_chain, int64_t first_step, int64_t steps,
+                   int32_t init, const double* step_eps, const double* kick_clip, int32_t n_leapfrog,
+                   int32_t noise_mode, uint64_t seed, double* z, double* log_u, int64_t noise_ld,
+                   int64_t noise_row0, const double* t_eval, int32_t t_n, const double* y_obs,
+                   const double* span_u0_tol, const double* whiten, double c_log, double norm_logc,
+                   const double* cov_inv, int64_t max_steps, double* samples, double* log_p, double* grad,
+                   int64_t out_ld, int64_t out_row0, void* stream) {
+    // the common checks (step_eps is their step size), then the sampler's own
+    st::LvHmcArgs a{};
+    int rc = lv_rwmh_args(a, state, chains, first_chain, first_step, steps, init, step_eps, noise_mode, seed, z,
+                          log_u, noise_ld, noise_row0, t_eval, t_n, y_obs, span_u0_tol, whiten, c_log, norm_logc,
+                          max_steps, samples, log_p, out_ld, out_row0);
+    if (rc) return rc;
+    if (!grad || !kick_clip || !cov_inv) return fail(ST_ERR_INVALID, "NULL pointer (grad, kick_clip, cov_inv)");
+    if (!aligned16(grad)) return fail(ST_ERR_INVALID, "grad must be 16-byte aligned");
+    for (int j = 0; j < 4; ++j)
+        if (!(kick_clip[j] > 0)) return fail(ST_ERR_INVALID, "kick clip %d must be > 0 (got %g)", j, kick_clip[j]);
+    if (n_leapfrog < 1) return fail(ST_ERR_INVALID, "n_leapfrog must be >= 1 (got %d)", (int)n_leapfrog);
+    for (int j = 0; j < 4; ++j) {
+        a.eps[j] = step_eps[j];
+        a.clip[j] = kick_clip[j];
+        a.cinv[j] = cov_inv[j];
+    }
+    a.n_leapfrog = n_leapfrog;
+    a.grad = grad;
+    return hip_check(st::launch_lv_hmc_wave(a, static_cast<hipStream_t>(stream)), "lv hmc wave launch");
+}
+
 int st_greedy_finalize(const double* cands_in, int32_t nranks, int32_t d, uint32_t* idx_out,
                        int64_t t, void* stream) {
     if (!cands_in || !idx_out) return fail(ST_ERR_INVALID, "NULL pointer");

@@ -450,6 +450,170 @@ __global__ __launch_bounds__(kWaveLanes * kWaveChainsPerBlock) void lv_mala_wave
     }
 }
 
+// ---- Hamiltonian Monte Carlo (HMC) sampler, one wave per chain ----
+// The chain runs in x = log theta with unit-variance momenta; the host hands over eps[4] (a vector eps is a diagonal
+// mass matrix), the kick cap c[4] (+inf: none) and the trajectory length L >= 1.  lp(x) and g(x) are
+// lv_mala_wave_kernel's: one lv_integrate<10> at theta = exp(x), the same per-lane sums and xor butterflies.  One
+// Metropolis step, every operation uncontracted and in this order:
+//   kick_j(q) = min(max(eps_j g_j(q), -c_j), c_j)   (mala_clip: a NaN stays a NaN),   hk_j(q) = 0.5 kick_j(q)
+//   r^0 = z (the step's four normals),   K(r) = 0.5 s,  s = sum_j r_j r_j from 0.0, j ascending
+//   stage l = 1 .. L from (q^0, r^0) = (x, z):
+//       r'  = r^(l-1) + hk(q^(l-1))
+//       q^l = q^(l-1) + eps r'                       (one multiply, one add per component)
+//       lp(q^l), g(q^l)                              (one integration)
+//       r^l = r' + hk(q^l)
+//   accept exactly when log_u < (lp(q^L) - lp(x)) + (K(r^0) - K(r^L))     (strict; a NaN anywhere rejects)
+// An interior kick is two half-kick additions, so a trajectory of L stages is, bit for bit, L one-stage trajectories
+// chained through (q, r).  The clipped force depends on q alone, so every stage stays a shear (reversible, volume-
+// preserving) and, with the true lp in the ratio, the chain still targets the posterior.  A stage whose theta has a
+// zero or non-finite component, or whose integration ends with a non-zero status, has lp = g = NaN: the NaN goes
+// through r into every later q of the trajectory, whose stages then run no integration, and the trajectory is
+// rejected and counted ONCE in n_failed.  Row t, log_p[t] and grad[t] = g(row t) are written for every row.
+// The step and stage loops are one flat loop (the start row is iteration -1), so the kernel has ONE lv_integrate<10>
+// call site.  Layout, noise, init, the 16-word state record, the summation order and the hand-off between launches
+// are lv_mala_wave_kernel's; a launch ends on a step boundary.  The butterflies run once per stage in every live
+// wave, outside any data-dependent branch; decisions come from lane 0's values (wave_first); lane 0 alone stores.
+template <bool DEVICE_NOISE, bool RECORD>
+__global__ __launch_bounds__(kWaveLanes * kWaveChainsPerBlock) void lv_hmc_wave_kernel(LvHmcArgs a) {
+    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x / kWaveLanes));
+    const int lane = (int)(threadIdx.x % kWaveLanes);
+    const int64_t i = (int64_t)blockIdx.x * kWaveChainsPerBlock + wave;
+    if (i >= a.chains) return;            // the whole wave (partial last block)
+    double* st = a.state + 16 * i;
+    int64_t* sti = reinterpret_cast<int64_t*>(st);
+    double x[4], g[4], lp;
+    {
+        const double2* s2 = reinterpret_cast<const double2*>(st);
+        const double2 s0 = s2[0], s1 = s2[1], g0 = s2[4], g1 = s2[5];
+        x[0] = s0.x; x[1] = s0.y; x[2] = s1.x; x[3] = s1.y;
+        g[0] = g0.x; g[1] = g0.y; g[2] = g1.x; g[3] = g1.y;
+    }
+    lp = st[4];
+    int64_t accepted = sti[5], failed = sti[6];
+    double* rows = a.samples + (i * a.out_ld + a.out_row0) * 4;
+    double* grads = a.grad + (i * a.out_ld + a.out_row0) * 4;
+    double* lps = a.log_p + i * a.out_ld + a.out_row0;
+    double* zs = nullptr;
+    double* lus = nullptr;
+    if (!DEVICE_NOISE || RECORD) {
+        zs = a.z + (i * a.noise_ld + a.noise_row0) * 4;
+        lus = a.log_u + i * a.noise_ld + a.noise_row0;
+    }
+    const uint64_t chain = (uint64_t)(a.first_chain + i);
+    // the trajectory: its current point q with g(q), its momentum r, K(r^0) and the step's log_u
+    double q[4], gq[4], r[4] = {0.0, 0.0, 0.0, 0.0}, k0 = 0.0, log_u = 0.0;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) { q[j] = x[j]; gq[j] = g[j]; }
+    int l = 0;                            // stages of step k done
+    // k = -1: the start row itself (a.init), evaluated by the same code as every stage
+#pragma unroll 1
+    for (int64_t k = a.init ? -1 : 0; k < a.steps;) {
+        const bool start = k < 0;
+        if (!start && l == 0) {
+            if constexpr (DEVICE_NOISE) {
+                device_noise(a.seed, chain, (uint64_t)(a.first_step + k), r, log_u);
+                if constexpr (RECORD) {
+                    if (lane == 0) {
+                        reinterpret_cast<double2*>(zs + 4 * k)[0] = make_double2(r[0], r[1]);
+                        reinterpret_cast<double2*>(zs + 4 * k)[1] = make_double2(r[2], r[3]);
+                        lus[k] = log_u;
+                    }
+                }
+            } else {
+                const double2 z01 = reinterpret_cast<const double2*>(zs + 4 * k)[0];
+                const double2 z23 = reinterpret_cast<const double2*>(zs + 4 * k)[1];
+                r[0] = z01.x; r[1] = z01.y; r[2] = z23.x; r[3] = z23.y;
+                log_u = lus[k];
+            }
+            double s = 0.0;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) s += r[j] * r[j];
+            k0 = 0.5 * s;
+        }
+        double rp[4], p[4], th[4];
+        bool ok = true;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            rp[j] = r[j] + 0.5 * mala_clip(a.eps[j] * gq[j], a.clip[j]);
+            p[j] = start ? q[j] : q[j] + a.eps[j] * rp[j];
+            th[j] = exp(p[j]);
+            ok = ok && isfinite(th[j]) && th[j] != 0.0;
+        }
+        double ll = 0.0, acc[4] = {0.0, 0.0, 0.0, 0.0};     // this lane's terms, in increasing k
+        int status = 0;
+        if (ok) {
+            int kq = lane;
+            double tq = lane < a.p.t_n ? a.p.t_eval[lane] : 0.0;
+            status = lv_integrate<10>(th, a.p, [&](double t_old, double t_new, double inv_hd, const double* y,
+                                                   const double (*Q)[rk45::kDenseOrder], bool last) {
+                lv_observe_strided<10>(a.p, kq, tq, kWaveLanes, t_old, t_new, inv_hd, y, Q, last,
+                                       [&](int kk, const double* u) {
+                                           ll += lv_loglik_term(a.p, kk, u);
+                                           lv_grad_term(a.p, a.cinv, kk, u, acc);
+                                       });
+                return 0;
+            });
+        }
+#pragma unroll
+        for (int off = kWaveLanes / 2; off >= 1; off >>= 1) {
+            ll += __shfl_xor(ll, off);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) acc[j] += __shfl_xor(acc[j], off);
+        }
+        double lp_new = NAN, g_new[4] = {NAN, NAN, NAN, NAN};   // theta out of range, or the integration failed
+        if (ok && status == 0) {
+            lp_new = wave_first(ll) + lv_log_prior(p, a.p.norm_logc);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) g_new[j] = th[j] * wave_first(acc[j]) - p[j];
+        }
+        if (start) {
+            lp = lp_new;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) g[j] = g_new[j];
+        } else {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                r[j] = rp[j] + 0.5 * mala_clip(a.eps[j] * g_new[j], a.clip[j]);
+                q[j] = p[j];
+                gq[j] = g_new[j];
+            }
+            if (++l < a.n_leapfrog) continue;
+            // the trajectory's end: a failed stage has made every later lp NaN
+            if (!(lp_new == lp_new)) ++failed;
+            double s = 0.0;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) s += r[j] * r[j];
+            if (log_u < (lp_new - lp) + (k0 - 0.5 * s)) {
+#pragma unroll
+                for (int j = 0; j < 4; ++j) { x[j] = q[j]; g[j] = gq[j]; }
+                lp = lp_new;
+                ++accepted;
+            }
+        }
+        if (lane == 0) {
+            reinterpret_cast<double2*>(rows + 4 * k)[0] = make_double2(x[0], x[1]);
+            reinterpret_cast<double2*>(rows + 4 * k)[1] = make_double2(x[2], x[3]);
+            reinterpret_cast<double2*>(grads + 4 * k)[0] = make_double2(g[0], g[1]);
+            reinterpret_cast<double2*>(grads + 4 * k)[1] = make_double2(g[2], g[3]);
+            lps[k] = lp;
+        }
+#pragma unroll
+        for (int j = 0; j < 4; ++j) { q[j] = x[j]; gq[j] = g[j]; }
+        l = 0;
+        ++k;
+    }
+    if (lane == 0) {
+        double2* s2 = reinterpret_cast<double2*>(st);
+        s2[0] = make_double2(x[0], x[1]);
+        s2[1] = make_double2(x[2], x[3]);
+        s2[4] = make_double2(g[0], g[1]);
+        s2[5] = make_double2(g[2], g[3]);
+        st[4] = lp;
+        sti[5] = accepted;
+        sti[6] = failed;
+    }
+}
+
 // kernel[noise_mode] (supplied, Philox, Philox + record) over a.chains chains, chains_per_block to a block
 template <class Args>
 hipError_t launch_noise_mode(void (*const (&kernel)[3])(Args), const Args& a, int chains_per_block,
@@ -465,6 +629,11 @@ constexpr unsigned kWaveThreads = kWaveLanes * kWaveChainsPerBlock;
 hipError_t launch_lv_mala_wave(const LvMalaArgs& a, hipStream_t s) {
     return launch_noise_mode<LvMalaArgs>({lv_mala_wave_kernel<false, false>, lv_mala_wave_kernel<true, false>,
                                           lv_mala_wave_kernel<true, true>}, a, kWaveChainsPerBlock, kWaveThreads, s);
+}
+
+hipError_t launch_lv_hmc_wave(const LvHmcArgs& a, hipStream_t s) {
+    return launch_noise_mode<LvHmcArgs>({lv_hmc_wave_kernel<false, false>, lv_hmc_wave_kernel<true, false>,
+                                         lv_hmc_wave_kernel<true, true>}, a, kWaveChainsPerBlock, kWaveThreads, s);
 }
 
 hipError_t launch_lv_rwmh_wave(const LvMcmcArgs& a, hipStream_t s) {

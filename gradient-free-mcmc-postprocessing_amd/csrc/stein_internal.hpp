@@ -246,6 +246,32 @@ struct LvMalaArgs {
 };
 hipError_t launch_lv_mala_wave(const LvMalaArgs& a, hipStream_t s);
 
+// Hamiltonian Monte Carlo sampler over the LV log posterior in x = log theta, one wave per chain
+// (csrc/lv_mcmc.hip: lv_hmc_wave_kernel); the fields it shares with LvMalaArgs mean the same
+struct LvHmcArgs {
+    double* state;            // (chains, 16) words, LvMalaArgs' record
+    int64_t chains;
+    int64_t first_chain;
+    int64_t first_step;
+    int64_t steps;            // Metropolis steps (trajectories) in this launch
+    int init;
+    double eps[4];            // leapfrog step size epsilon
+    double clip[4];           // kick cap c (> 0, may be +inf): bounds every component of eps * g
+    int n_leapfrog;           // leapfrog stages per trajectory, L >= 1
+    int noise_mode;
+    uint64_t seed;
+    double* z;
+    double* log_u;
+    int64_t noise_ld, noise_row0;
+    LvProblem p;
+    double cinv[4];           // inv(C) row-major
+    double* samples;          // (chains, out_ld, 4)
+    double* log_p;            // (chains, out_ld)
+    double* grad;             // (chains, out_ld, 4)
+    int64_t out_ld, out_row0;
+};
+hipError_t launch_lv_hmc_wave(const LvHmcArgs& a, hipStream_t s);
+
 hipError_t launch_greedy_rank_exchange(const double* recs, int K, int64_t stride, int d,
                                        const MailboxPeers& peers, int rank, int nranks, int64_t t,
                                        double* recv, unsigned* status, hipStream_t s);

@@ -113,6 +113,11 @@ SIGNATURES = {
     'st_lv_mala_wave': (ctypes.c_int, [_c_dp, _i64, _i64, _i64, _i64, _i32, _c_dp, _c_dp, _i32, ctypes.c_uint64,
                                        _c_dp, _c_dp, _i64, _i64, _c_dp, _i32, _c_dp, _c_dp, _c_dp, _f64, _f64,
                                        _c_dp, _i64, _c_dp, _c_dp, _c_dp, _i64, _i64, _c_dp]),
+    'st_lv_hmc_workspace_bytes': (_i64, [_i64]),
+    # step_eps, kick_clip, span_u0_tol, whiten, cov_inv: host arrays; seed: uint64
+    'st_lv_hmc_wave': (ctypes.c_int, [_c_dp, _i64, _i64, _i64, _i64, _i32, _c_dp, _c_dp, _i32, _i32, ctypes.c_uint64,
+                                      _c_dp, _c_dp, _i64, _i64, _c_dp, _i32, _c_dp, _c_dp, _c_dp, _f64, _f64,
+                                      _c_dp, _i64, _c_dp, _c_dp, _c_dp, _i64, _i64, _c_dp]),
     'st_kde_workspace_bytes': (_i64, [_i64, _i32]),
     'st_kde_logpdf_grad': (ctypes.c_int, [_c_dp, _i64, _i64, _c_dp, _f64, _c_dp, _i64, _i64, _i32, _f64, _c_dp,
                                           _c_dp, _c_dp, _c_dp, _i64, _c_dp]),

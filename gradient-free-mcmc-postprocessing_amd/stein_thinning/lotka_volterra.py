@@ -472,3 +472,88 @@ def mala_sample(log_theta_init, n_samples, step_size, *, seed=None, noise=None, 
         failed_start='mala_sample: the evaluation', x0=x0, n_samples=n_samples, seed=seed, noise=noise,
         first_chain=first_chain, spl=spl, max_steps=max_steps, problem=problem, return_noise=return_noise,
         device_out=device_out, state_words=16, n_extra=1, launch=launch))
+
+
+def STEPS_PER_LAUNCH_HMC(n_leapfrog: int) -> int:
+    """Metropolis steps per launch of ``hmc_sample`` for trajectories of ``n_leapfrog`` stages."""
+    # 64 leapfrog stages per launch, first an estimate from MALA's 0.18 ms per gradient evaluation, then MEASURED on
+    # MI355X (tools/lv_hmc_bench.py, profiles/lv_hmc_bench.json: eps 0.001, kick cap 0.5, starts near the mode, L = 1,
+    # 4 and 16): a launch of 64 stages takes 0.012-0.013 s at 5 to 1024 chains (0.18-0.20 ms per stage) and 0.048-0.049 s
+    # at 4096 (0.73-0.75 ms), as MALA's 64 steps do, and 0.025 s from the reference's far starts -- far below the
+    # quarter of a second, with room for integrations that take several times the steps.  A trajectory longer than
+    # 64 stages is one launch per step.  Other splits were not timed.  Results do not depend on it.
+    return max(1, 64 // int(n_leapfrog))
+
+
+@dataclass
+class HmcSample:
+    """Result of ``hmc_sample`` (NumPy arrays, or ROCm tensors with ``device_out=True``)."""
+    samples: object                   # (chains, n_samples, 4) log theta; row 0 is the start
+    log_p: object                     # (chains, n_samples) log target density of every row (10-state solution)
+    grad: object                      # (chains, n_samples, 4) gradient of log p with respect to log theta
+    accepted: object                  # (chains,) int64: accepted trajectories
+    n_failed: object                  # (chains,) int64: trajectories rejected because a stage had no density
+    z: object = None                  # (chains, n_samples - 1, 4): the normal noise used (return_noise)
+    log_u: object = None              # (chains, n_samples - 1): the log uniforms used (return_noise)
+
+
+def hmc_sample(log_theta_init, n_samples, step_size, n_leapfrog, *, seed=None, noise=None,
+               kick_cap: float = math.inf, data: Optional[LvData] = None, rtol: float = RTOL, atol: float = ATOL,
+               max_steps: int = MAX_STEPS, first_chain: int = 0, steps_per_launch: Optional[int] = None,
+               return_noise: bool = False, device_out: bool = False) -> HmcSample:
+    """Hamiltonian Monte Carlo (HMC) chains on the LV log posterior, one chain per GPU wave (``st_lv_hmc_wave``,
+    csrc/lv_mcmc.hip): the gradient-based stage of the reference's ``Sampling.ipynb``, which uses Stan's HMC.  Stan
+    is not part of the reference's tree, so the sampler is this project's own definition: a fixed trajectory
+    length and a fixed step size, no adaptation.  As with ``mala_sample`` every row leaves with ``log_p`` and
+    ``grad``, so ``thin_chains(list(run.samples), list(run.grad), m)`` needs no further pass.
+
+    Definition.  The chain runs in x = log theta with unit-variance momenta; ``step_size`` is eps, a scalar or a
+    (4,) vector (a vector eps is a diagonal mass matrix), ``n_leapfrog`` = L >= 1 the stages of a trajectory and
+    ``kick_cap`` > 0 (default inf: none) the bound c on every component of eps * g.  lp(x) and g(x) are
+    ``mala_sample``'s: one 10-state RK45 integration at theta = exp(x).  With hk(q) = 0.5 * clip(eps * g(q), -c, c)
+    and K(r) = 0.5 * sum_j r_j r_j, one step draws r^0 = z (the step's four normals), runs from (q^0, r^0) = (x, z)
+    the stages ``r' = r + hk(q); q = q + eps * r'; r = r' + hk(q)`` (one multiply and one add per component, an
+    interior kick as two half-kick additions) and accepts q^L exactly when
+    ``log_u < (lp(q^L) - lp(x)) + (K(r^0) - K(r^L))``; the comparison is strict and a NaN anywhere rejects.  A
+    trajectory of L stages is therefore, bit for bit, L one-stage trajectories chained through (q, r).  With
+    L = 1 the proposal is MALA's up to rounding.  The capped force depends on q alone, so every stage stays a
+    shear: the map is reversible and volume-preserving, and with the true lp in the ratio the chain still targets
+    the posterior.  ``kick_cap`` plays ``drift_cap``'s role: from far starts eps * g is ~1e2 and an uncapped
+    trajectory is thrown to theta where integrations take very long.  Nothing in the reference fixes eps or L;
+    measured with the reference data (5 chains of 128 steps from starts 0.02 off log(THETA), ``kick_cap=0.5``,
+    profiles/lv_hmc_bench.json): acceptance 0.68 / 0.59 / 0.46 for L = 1 / 4 / 16 at eps 0.001, 0.83 / 0.83 / 0.76 at
+    0.0005, 0.42 / 0.29 / 0.11 at 0.002.
+
+    A stage whose theta has a zero or non-finite component, or whose integration fails, fails its whole
+    trajectory: it is rejected and counted once in ``n_failed``, and its later stages run no integration.  A START
+    whose own evaluation fails raises ValueError.
+
+    Noise, ``seed``, ``noise=(z, log_u)``, ``first_chain``, ``return_noise`` and ``device_out`` are ``rw_sample``'s:
+    for one seed and chain id the noise is the same, bit for bit (one set of four normals and one log uniform
+    per step, whatever L is).  ``steps_per_launch`` (default ``STEPS_PER_LAUNCH_HMC(n_leapfrog)``) splits the run
+    into launches; the result does not depend on it.  The summation order is ``mala_sample``'s; a chain is
+    bit-identical to itself under any launch split, any ``first_chain`` offset, with or without ``return_noise``,
+    and when re-run from its recorded noise."""
+    x0, n_samples, eps = _chain_start(log_theta_init, n_samples, step_size)
+    if isinstance(n_leapfrog, bool) or not isinstance(n_leapfrog, (int, np.integer)) or not 1 <= n_leapfrog < 2 ** 31:
+        raise ValueError(f'n_leapfrog must be an integer >= 1, got {n_leapfrog!r}')
+    n_leapfrog = int(n_leapfrog)
+    try:
+        cap = float(kick_cap)
+    except (TypeError, ValueError):
+        raise ValueError(f'kick_cap must be a number > 0, got {kick_cap!r}') from None
+    if isinstance(kick_cap, bool) or not cap > 0:
+        raise ValueError(f'kick_cap must be > 0 (inf: no cap), got {kick_cap!r}')
+    clip = np.full(4, cap)
+    seed, noise, spl = _chain_noise(x0.shape[0], n_samples - 1, seed, noise, first_chain, steps_per_launch,
+                                    STEPS_PER_LAUNCH_HMC(n_leapfrog), max_steps)
+    problem = _chain_problem(data, rtol, atol)
+    cinv = np.ascontiguousarray(np.linalg.inv(np.asarray(problem[0].cov, dtype=np.float64)))
+
+    def launch(L, head, mid, rows, extra, tail):
+        nat.check(L.st_lv_hmc_wave(*head, eps.ctypes.data, clip.ctypes.data, n_leapfrog, *mid, cinv.ctypes.data, *rows,
+                                   *extra, *tail), 'st_lv_hmc_wave')
+    return HmcSample(*_run_chains(
+        failed_start='hmc_sample: the evaluation', x0=x0, n_samples=n_samples, seed=seed, noise=noise,
+        first_chain=first_chain, spl=spl, max_steps=max_steps, problem=problem, return_noise=return_noise,
+        device_out=device_out, state_words=16, n_extra=1, launch=launch))

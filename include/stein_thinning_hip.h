@@ -493,6 +493,48 @@ int st_lv_mala_wave(double *state, int64_t chains, int64_t first_chain, int64_t 
                     int64_t out_row0, void *stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Hamiltonian Monte Carlo (HMC) sampler for the LV log posterior, one WAVE per chain
+ * (csrc/lv_mcmc.hip: lv_hmc_wave_kernel): a Metropolis step whose proposal is a trajectory of n_leapfrog
+ * leapfrog stages; st_lv_mala_wave's proposal is its one-stage case up to rounding.  Stan's sampler is not part
+ * of the reference's tree; this is the project's own definition:
+ *   The chain runs in x = log theta with unit-variance momenta.  eps[4] is the step size (a vector eps is a
+ *   diagonal mass matrix), c[4] the kick cap (+inf: none), L = n_leapfrog >= 1.  lp(x) and g(x) are
+ *   st_lv_mala_wave's (one 10-state integration at theta = exp(x), the same summation order).  All device
+ *   arithmetic is uncontracted and in this order, at global step t = first_step + k:
+ *     kick_j(q) = min(max(eps_j g_j(q), -c_j), c_j)     (two comparisons: a NaN stays a NaN)
+ *     hk_j(q)   = 0.5 kick_j(q)
+ *     r^0 = z, the step's four normals;   K(r) = 0.5 s,  s = sum_j r_j r_j from 0.0, j ascending
+ *     stage l = 1 .. L from (q^0, r^0) = (x, z):
+ *       r'  = r^(l-1) + hk(q^(l-1))
+ *       q^l = q^(l-1) + eps r'                           (one multiply and one add per component)
+ *       lp(q^l), g(q^l)
+ *       r^l = r' + hk(q^l)
+ *     accept exactly when log_u < (lp(q^L) - lp(x)) + (K(r^0) - K(r^L))    (strict; a NaN anywhere rejects)
+ *   An interior kick is two half-kick additions, so a trajectory of L stages is, bit for bit, L one-stage
+ *   trajectories chained through (q, r).  The capped force depends on q alone: every stage stays a shear, the
+ *   map reversible and volume-preserving, and with the true lp in the ratio the chain targets the posterior.
+ *   A stage fails when its theta has a zero or non-finite component or its integration ends with a non-zero
+ *   status; its NaN gradient carries through the later q of the trajectory, whose stages run no integration;
+ *   the trajectory is rejected and counted ONCE in n_failed.  Row out_row0 + k of samples, log_p and grad
+ *   (= g of that row) is written.
+ * Arguments as st_lv_mala_wave (layout, summation order, noise modes, Philox keys and counters, init,
+ * first_step, first_chain, out_row0, noise_row0 and the 16-word state record included: for one seed the noise
+ * is st_lv_rwmh's), except:
+ *   state: st_lv_hmc_workspace_bytes(chains) = 128 chains bytes;
+ *   step_eps: HOST (4) = eps;  kick_clip: HOST (4) = c (may be +inf);  n_leapfrog: L.
+ * ST_ERR_INVALID (all checked before any HIP call): the conditions of st_lv_rwmh (eps is its step size); grad
+ * NULL or not 16-byte aligned; kick_clip or cov_inv NULL; a c that is NaN or <= 0; n_leapfrog < 1.
+ * ---------------------------------------------------------------------------------------- */
+int64_t st_lv_hmc_workspace_bytes(int64_t chains);
+int st_lv_hmc_wave(double *state, int64_t chains, int64_t first_chain, int64_t first_step, int64_t steps,
+                   int32_t init, const double *step_eps, const double *kick_clip, int32_t n_leapfrog,
+                   int32_t noise_mode, uint64_t seed, double *z, double *log_u, int64_t noise_ld,
+                   int64_t noise_row0, const double *t_eval, int32_t t_n, const double *y_obs,
+                   const double *span_u0_tol, const double *whiten, double c_log, double norm_logc,
+                   const double *cov_inv, int64_t max_steps, double *samples, double *log_p, double *grad,
+                   int64_t out_ld, int64_t out_row0, void *stream);
+
+/* ------------------------------------------------------------------------------------------
  * Integrand protocol -- replaces integrand(ind1, ind2) of the closures returned by
  * stein_thinning.thinning._make_stein_integrand / _make_stein_gf_integrand and
  * stein_thinning.kernel.vfk0_imq (restated at JAX_Stein_Thinning.ipynb cell 27, json ~354-361;
