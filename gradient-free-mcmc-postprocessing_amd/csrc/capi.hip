@@ -459,6 +459,24 @@ int lv_rwmh(hipError_t (*launch)(const st::LvMcmcArgs&, hipStream_t), const char
     return hip_check(launch(a, static_cast<hipStream_t>(stream)), what);
 }
 
+// st_autocov / st_autocov_workspace_bytes: the shape checks both share (0 ok)
+int check_autocov_shape(int64_t groups, int64_t S, int64_t h, int64_t lag0, int64_t lag1, int32_t plan) {
+    if (groups < 1) return fail(ST_ERR_INVALID, "groups must be >= 1 (got %lld)", (long long)groups);
+    if (S < 1) return fail(ST_ERR_INVALID, "S must be >= 1 (got %lld)", (long long)S);
+    if (h < 4) return fail(ST_ERR_INVALID, "h must be >= 4 (got %lld)", (long long)h);
+    if (lag0 < 0 || lag0 >= lag1)
+        return fail(ST_ERR_INVALID, "need 0 <= lag0 < lag1 (got %lld, %lld)", (long long)lag0, (long long)lag1);
+    if (lag1 > h) return fail(ST_ERR_INVALID, "lag1 must be <= h (got %lld > %lld)", (long long)lag1, (long long)h);
+    if (plan < 0 || plan > 2) return fail(ST_ERR_INVALID, "plan must be 0 (by shape), 1 (long) or 2 (short)");
+    if (S > ((int64_t)1 << 40) / groups || h > ((int64_t)1 << 40) / (groups * S))
+        return fail(ST_ERR_UNSUPPORTED, "groups * S * h exceeds 2^40");
+    if (plan == 2 && !st::autocov_short_ok(h))
+        return fail(ST_ERR_UNSUPPORTED, "the short plan holds a series in LDS: h = %lld is too long", (long long)h);
+    if (!st::autocov_grid_ok(groups, S, h, lag0, lag1, plan))
+        return fail(ST_ERR_UNSUPPORTED, "too many series or lags for one launch");
+    return ST_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1241,6 +1259,46 @@ int st_run_compact(const double* x_soa, const double* g_soa, const double* weigh
                                             x_out, g_out, weights ? w_out : nullptr, rows_out,
                                             static_cast<hipStream_t>(stream)),
                      "run-compact launch");
+}
+
+int st_rank_normalize(const double* sorted, const int64_t* perm, int64_t vars, int64_t count, double* p_out,
+                      double* z_out, void* stream) {
+    if (!sorted || !perm || !z_out) return fail(ST_ERR_INVALID, "NULL pointer");
+    if (!aligned8(sorted) || !aligned8(perm) || !aligned8(z_out) || (p_out && !aligned8(p_out)))
+        return fail(ST_ERR_INVALID, "device arrays must be 8-byte aligned");
+    if (vars < 1) return fail(ST_ERR_INVALID, "vars must be >= 1 (got %lld)", (long long)vars);
+    if (count < 1) return fail(ST_ERR_INVALID, "count must be >= 1 (got %lld)", (long long)count);
+    if (count > ((int64_t)1 << 38) / vars) return fail(ST_ERR_UNSUPPORTED, "vars * count exceeds 2^38");
+    st::RankArgs a{sorted, perm, vars, count, p_out, z_out};
+    return hip_check(st::launch_rank_normalize(a, static_cast<hipStream_t>(stream)), "rank-normalize launch");
+}
+
+int64_t st_autocov_workspace_bytes(int64_t groups, int64_t S, int64_t h, int64_t lag0, int64_t lag1, int32_t plan) {
+    if (check_autocov_shape(groups, S, h, lag0, lag1, plan)) return -1;
+    return st::autocov_ws_bytes(groups, S, h, lag0, lag1, plan);
+}
+
+int st_autocov(const double* series, int64_t groups, int64_t S, int64_t h, int64_t lag0, int64_t lag1, int32_t plan,
+               double* acov_mean, double* series_mean, double* series_var0, double* acov_series, void* workspace,
+               int64_t workspace_bytes, void* stream) {
+    if (!series || !acov_mean || !series_mean || !series_var0 || !workspace)
+        return fail(ST_ERR_INVALID, "NULL pointer");
+    if (!aligned8(series) || !aligned8(acov_mean) || !aligned8(series_mean) || !aligned8(series_var0) ||
+        !aligned8(workspace) || (acov_series && !aligned8(acov_series)))
+        return fail(ST_ERR_INVALID, "device arrays must be 8-byte aligned");
+    int rc = check_autocov_shape(groups, S, h, lag0, lag1, plan);
+    if (rc) return rc;
+    const int64_t need = st::autocov_ws_bytes(groups, S, h, lag0, lag1, plan);
+    if (workspace_bytes < need)
+        return fail(ST_ERR_INVALID, "workspace too small (%lld < %lld)", (long long)workspace_bytes, (long long)need);
+    st::AutocovArgs a{series, groups, S, h, lag0, lag1, plan, acov_mean, series_mean, series_var0, acov_series,
+                      static_cast<double*>(workspace)};
+    return hip_check(st::launch_autocov(a, static_cast<hipStream_t>(stream)), "autocov launch");
+}
+
+int st_autocov_plan(int64_t groups, int64_t S, int64_t h, int64_t lag0, int64_t lag1, int32_t plan) {
+    if (check_autocov_shape(groups, S, h, lag0, lag1, plan)) return -1;
+    return st::autocov_plan(groups, S, h, lag0, lag1, plan);
 }
 
 }  // extern "C"

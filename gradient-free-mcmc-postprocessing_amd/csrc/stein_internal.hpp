@@ -327,4 +327,29 @@ hipError_t launch_run_compact(const double* x, const double* g, const double* w,
                               const uint8_t* starts, const int32_t* tile_off, int64_t count, int64_t ld_out,
                               double* xo, double* go, double* wo, int32_t* rows_out, hipStream_t s);
 
+// convergence diagnostics (convergence.hip)
+struct RankArgs {
+    const double* sorted;   // (vars, N) each row ascending (NaN last)
+    const int64_t* perm;    // (vars, N) original position of every sorted value
+    int64_t vars, N;
+    double* p_out;          // (vars, N) at the original positions, or nullptr
+    double* z_out;          // (vars, N) at the original positions
+};
+hipError_t launch_rank_normalize(const RankArgs& a, hipStream_t s);
+struct AutocovArgs {
+    const double* series;   // (G, S, h) contiguous
+    int64_t G, S, h, lag0, lag1;
+    int plan;               // 0: by shape, 1: long, 2: short
+    double* acov_mean;      // (G, lag1 - lag0)
+    double* series_mean;    // (G, S)
+    double* series_var0;    // (G, S)
+    double* acov_series;    // (G, S, lag1 - lag0) or nullptr
+    double* ws;
+};
+int autocov_plan(int64_t G, int64_t S, int64_t h, int64_t lag0, int64_t lag1, int want);   // 1 long, 2 short
+bool autocov_short_ok(int64_t h);
+bool autocov_grid_ok(int64_t G, int64_t S, int64_t h, int64_t lag0, int64_t lag1, int want);
+int64_t autocov_ws_bytes(int64_t G, int64_t S, int64_t h, int64_t lag0, int64_t lag1, int want);
+hipError_t launch_autocov(const AutocovArgs& a, hipStream_t s);
+
 }  // namespace st

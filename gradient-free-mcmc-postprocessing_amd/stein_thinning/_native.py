@@ -154,6 +154,12 @@ SIGNATURES = {
                                       _c_dp, _c_dp]),
     'st_greedy_many_max_n': (_i64, [_i32, _i32]),
     'st_greedy_many_plan': (ctypes.c_int, [_i64, _i32, _i32, ctypes.POINTER(_i32), ctypes.POINTER(_i32)]),
+    # convergence diagnostics (csrc/convergence.hip)
+    'st_rank_normalize': (ctypes.c_int, [_c_dp, _c_dp, _i64, _i64, _c_dp, _c_dp, _c_dp]),
+    'st_autocov_workspace_bytes': (_i64, [_i64, _i64, _i64, _i64, _i64, _i32]),
+    'st_autocov_plan': (ctypes.c_int, [_i64, _i64, _i64, _i64, _i64, _i32]),
+    'st_autocov': (ctypes.c_int, [_c_dp, _i64, _i64, _i64, _i64, _i64, _i32, _c_dp, _c_dp, _c_dp, _c_dp, _c_dp,
+                                  _i64, _c_dp]),
 }
 ABI_VERSION = 1
 

@@ -804,6 +804,39 @@ int64_t st_greedy_many_max_n(int32_t d, int32_t has_weights);
 int st_greedy_many_plan(int64_t n, int32_t d, int32_t has_weights, int32_t *threads_out,
                         int32_t *rows_out);
 
+/* ----------------------------------------------------------------------------------------------
+ * Convergence diagnostics (csrc/convergence.hip; stein_thinning.convergence)
+ *
+ * st_rank_normalize: sorted (vars, count) holds every variable's values in ascending order (NaN last)
+ * and perm (vars, count) the original position of each, as a stable sort returns them.  For every value
+ * the kernel finds its tie run, the run's average 1-based rank r, p = (r - 0.375) / (count + 0.25) (one
+ * exact subtraction, one IEEE division) and z = the inverse normal cdf of p (AS241 PPND16), and writes z
+ * (and p, when p_out is given) at the value's original position of a (vars, count) array.  A NaN value
+ * gives NaN.  A perm entry outside [0, count) writes nothing.
+ * ST_ERR_INVALID: NULL or not 8-byte aligned pointers, vars < 1, count < 1.
+ *
+ * st_autocov: series (groups, S, h) contiguous.  For every series s of group g, with mu its mean,
+ *     acov[g, s, t] = (1 / h) sum_{i < h - t} (a[i] - mu) (a[i + t] - mu),   lag0 <= t < lag1;
+ * acov_mean[g, t - lag0] = the mean over the group's series (slabs of 256 series, each in series order,
+ * the slabs in order), series_mean[g, s] = mu, series_var0[g, s] = acov[g, s, 0] (its own sum, whatever
+ * lag0 is), acov_series (groups, S, lag1 - lag0) the per-series values when given (NULL: not written).
+ * plan 0 chooses by shape, 1 is the long plan (blocks tile i chunks x lag tiles, any h), 2 the short
+ * plan (a wave per series, the series in LDS, h <= 2048); st_autocov_plan returns the plan a call
+ * would take.  No atomics: the same arguments give the same bits on every call and every device.
+ * workspace: st_autocov_workspace_bytes(...) bytes (host only; -1 for arguments st_autocov rejects).
+ * ST_ERR_INVALID: NULL or not 8-byte aligned pointers, groups < 1, S < 1, h < 4, lag0 < 0,
+ * lag0 >= lag1, lag1 > h, plan outside 0..2, a workspace that is too small.  ST_ERR_UNSUPPORTED: the
+ * short plan with h > 2048, more series or lags than one launch holds.  All checked before any HIP call.
+ * ---------------------------------------------------------------------------------------------- */
+int st_rank_normalize(const double *sorted, const int64_t *perm, int64_t vars, int64_t count,
+                      double *p_out /* or NULL */, double *z_out, void *stream);
+int64_t st_autocov_workspace_bytes(int64_t groups, int64_t S, int64_t h, int64_t lag0, int64_t lag1,
+                                   int32_t plan);
+int st_autocov_plan(int64_t groups, int64_t S, int64_t h, int64_t lag0, int64_t lag1, int32_t plan);
+int st_autocov(const double *series, int64_t groups, int64_t S, int64_t h, int64_t lag0, int64_t lag1,
+               int32_t plan, double *acov_mean, double *series_mean, double *series_var0,
+               double *acov_series /* or NULL */, void *workspace, int64_t workspace_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
