@@ -386,14 +386,15 @@ int lv_grad(const double* theta, int64_t n, const double* t_eval, int32_t t_n, c
 }
 
 // the LV samplers' common checks (all before any HIP call) and the kernel arguments that LvMcmcArgs and
-// LvMalaArgs share, once; step_size: the random walk's step, MALA's eps (checked here, copied by the caller)
+// LvMalaArgs share, once; step_size: the random walk's step, MALA's eps (checked here, copied by the caller);
+// host_step false: the sampler's step sizes are device arrays, which it checks for NULL itself
 template <class Args>
 int lv_rwmh_args(Args& a, double* state, int64_t chains, int64_t first_chain, int64_t first_step,
                  int64_t steps, int32_t init, const double* step_size, int32_t noise_mode, uint64_t seed,
                  double* z, double* log_u, int64_t noise_ld, int64_t noise_row0, const double* t_eval,
                  int32_t t_n, const double* y_obs, const double* span_u0_tol, const double* whiten,
                  double c_log, double norm_logc, int64_t max_steps, double* samples, double* log_p,
-                 int64_t out_ld, int64_t out_row0) {
+                 int64_t out_ld, int64_t out_row0, bool host_step = true) {
     if (chains < 1) return fail(ST_ERR_INVALID, "chains must be >= 1 (got %lld)", (long long)chains);
     if (steps < 1) return fail(ST_ERR_INVALID, "steps must be >= 1 (got %lld)", (long long)steps);
     int rc = lv_problem(a.p, t_eval, t_n, y_obs, span_u0_tol, whiten, c_log, norm_logc, max_steps, true);
@@ -403,7 +404,7 @@ int lv_rwmh_args(Args& a, double* state, int64_t chains, int64_t first_chain, in
     if (init != 0 && init != 1) return fail(ST_ERR_INVALID, "init must be 0 or 1");
     if (noise_mode < 0 || noise_mode > 2) return fail(ST_ERR_INVALID, "noise_mode must be 0, 1 or 2");
     if (!state || !samples || !log_p) return fail(ST_ERR_INVALID, "NULL pointer");
-    if (!step_size || !whiten) return fail(ST_ERR_INVALID, "NULL host settings");
+    if ((host_step && !step_size) || !whiten) return fail(ST_ERR_INVALID, "NULL host settings");
     if (noise_mode != 1) {
         if (!z || !log_u)
             return fail(ST_ERR_INVALID, "NULL noise arrays (z, log_u): noise_mode %d needs them", noise_mode);
@@ -421,7 +422,7 @@ int lv_rwmh_args(Args& a, double* state, int64_t chains, int64_t first_chain, in
         return fail(ST_ERR_INVALID, "output rows [%lld, %lld) outside the output arrays' %lld rows",
                     (long long)(out_row0 - init), (long long)(out_row0 + steps), (long long)out_ld);
     if (init && first_step != 1) return fail(ST_ERR_INVALID, "init needs first_step = 1");
-    for (int j = 0; j < 4; ++j)
+    for (int j = 0; host_step && j < 4; ++j)
         if (!isfinite(step_size[j]) || !(step_size[j] > 0))
             return fail(ST_ERR_INVALID, "step size %d must be finite and > 0 (got %g)", j, step_size[j]);
     a.state = state;
@@ -1009,6 +1010,51 @@ int st_lv_hmc_wave(double* state, int64_t chains, int64_t first_chain, int64_t f
     a.n_leapfrog = n_leapfrog;
     a.grad = grad;
     return hip_check(st::launch_lv_hmc_wave(a, static_cast<hipStream_t>(stream)), "lv hmc wave launch");
+}
+
+int64_t st_lv_hmc_metric_workspace_bytes(int64_t chains) {
+    if (chains < 1) return -1;
+    return chains * 192;
+}
+
+int st_lv_hmc_metric_wave(double* state, int64_t chains, int64_t first_chain, int64_t first_step, int64_t steps,
+                          int32_t init, const double* eps_chain, const double* metric_chol, const double* kick_clip,
+                          int32_t n_leapfrog, int32_t adapt, double delta, int32_t noise_mode, uint64_t seed,
+                          double* z, double* log_u, int64_t noise_ld, int64_t noise_row0, const double* t_eval,
+                          int32_t t_n, const double* y_obs, const double* span_u0_tol, const double* whiten,
+                          double c_log, double norm_logc, const double* cov_inv, int64_t max_steps, double* samples,
+                          double* log_p, double* grad, double* accept_stat, double* step_size, int64_t out_ld,
+                          int64_t out_row0, void* stream) {
+    // the common checks (the step sizes are a device array: not theirs), then the sampler's own
+    st::LvHmcMetricArgs a{};
+    int rc = lv_rwmh_args(a, state, chains, first_chain, first_step, steps, init, nullptr, noise_mode, seed, z,
+                          log_u, noise_ld, noise_row0, t_eval, t_n, y_obs, span_u0_tol, whiten, c_log, norm_logc,
+                          max_steps, samples, log_p, out_ld, out_row0, false);
+    if (rc) return rc;
+    if (!grad || !kick_clip || !cov_inv) return fail(ST_ERR_INVALID, "NULL pointer (grad, kick_clip, cov_inv)");
+    if (!eps_chain || !metric_chol || !accept_stat || !step_size)
+        return fail(ST_ERR_INVALID, "NULL pointer (eps_chain, metric_chol, accept_stat, step_size)");
+    if (!aligned16(grad)) return fail(ST_ERR_INVALID, "grad must be 16-byte aligned");
+    if (!aligned8(eps_chain) || !aligned8(metric_chol) || !aligned8(accept_stat) || !aligned8(step_size))
+        return fail(ST_ERR_INVALID, "eps_chain, metric_chol, accept_stat and step_size must be 8-byte aligned");
+    for (int j = 0; j < 4; ++j)
+        if (!(kick_clip[j] > 0)) return fail(ST_ERR_INVALID, "kick clip %d must be > 0 (got %g)", j, kick_clip[j]);
+    if (n_leapfrog < 1) return fail(ST_ERR_INVALID, "n_leapfrog must be >= 1 (got %d)", (int)n_leapfrog);
+    if (adapt != 0 && adapt != 1) return fail(ST_ERR_INVALID, "adapt must be 0 or 1");
+    if (!(delta > 0 && delta < 1)) return fail(ST_ERR_INVALID, "delta must lie in (0, 1) (got %g)", delta);
+    for (int j = 0; j < 4; ++j) {
+        a.clip[j] = kick_clip[j];
+        a.cinv[j] = cov_inv[j];
+    }
+    a.eps_chain = eps_chain;
+    a.metric_chol = metric_chol;
+    a.n_leapfrog = n_leapfrog;
+    a.adapt = adapt;
+    a.delta = delta;
+    a.grad = grad;
+    a.accept_stat = accept_stat;
+    a.step_size = step_size;
+    return hip_check(st::launch_lv_hmc_metric_wave(a, static_cast<hipStream_t>(stream)), "lv hmc metric wave launch");
 }
 
 int st_greedy_finalize(const double* cands_in, int32_t nranks, int32_t d, uint32_t* idx_out,

@@ -614,6 +614,218 @@ __global__ __launch_bounds__(kWaveLanes * kWaveChainsPerBlock) void lv_hmc_wave_
     }
 }
 
+// ---- HMC with a per-chain step size and a dense metric, with step-size adaptation ----
+// lv_hmc_wave_kernel's definition with three additions; every operation uncontracted and in the stated order.
+// (1) eps is a scalar per chain and the metric a per-chain factor Lam (lower triangular, M^-1 = Lam Lam^T), both read
+// from device memory: a.eps_chain[i] and the packed row-major lower triangle a.metric_chol[10 i ..] (Lam_jk at
+// j (j + 1) / 2 + k).  The momentum stays r ~ N(0, I): the noise and K(r) are unchanged.  In a stage
+//   f_j(q)    = Lam_jj g_j(q) + sum_{k > j} Lam_kj g_k(q)        (the first term alone, then k ascending)
+//   kick_j(q) = min(max(eps f_j(q), -c_j), c_j),   hk = 0.5 kick
+//   r'  = r + hk(q);   v_j = sum_{k <= j} Lam_jk r'_k  (from the k = 0 term, k ascending);   q_j <- q_j + eps v_j
+//   r   = r' + hk(q)                                             (at the new q)
+// which is unit-mass HMC in y = Lam^-1 x: the clipped force depends on q alone, so every stage stays a shear.  Lam is
+// read again in every stage (uniform loads), not kept across the integration.
+// (2) per step, a.accept_stat = alpha = min(1, exp(a)), a = (lp(q^L) - lp(x)) + (K(r^0) - K(r^L)), 0 when a is NaN, and
+// a.step_size = the eps the step used (rows out_row0 + k of (chains, out_ld) arrays; the start row has none).
+// (3) a.adapt = 1: eps comes from the state record and follows Stan's dual averaging after every step (delta handed
+// over, gamma 0.05, t0 10, kappa 0.75):  m <- m + 1;  eta = 1 / (m + t0);  sbar <- (1 - eta) sbar + eta (delta - alpha);
+// ell = mu - (sbar sqrt(m)) / gamma;  w = pow(m, -kappa);  xbar <- (1 - w) xbar + w ell;  eps <- exp(ell).
+// The state record has 24 words per chain: LvMalaArgs' 16, then eps, m, sbar, xbar, mu and three spare.  The five are
+// loaded and stored at the step's end -- only eps is live across the integration -- by EVERY lane (the same bits to the
+// same address), so that each lane reads back what it wrote itself.  With a.adapt = 0 they are neither read nor
+// written and eps stays a.eps_chain[i].  A launch ends on a step boundary with the whole state in the record.
+constexpr int kHmcMetricStateWords = 24;
+constexpr double kDaGamma = 0.05, kDaT0 = 10.0, kDaKappa = 0.75;
+
+// hk(q) from g(q): the force through Lam^T, the cap, the half
+__device__ __forceinline__ void metric_half_kick(const double* lam, const double g[4], double eps, const double c[4],
+                                                 double hk[4]) {
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        double f = lam[j * (j + 1) / 2 + j] * g[j];
+#pragma unroll
+        for (int k = j + 1; k < 4; ++k) f += lam[k * (k + 1) / 2 + j] * g[k];
+        hk[j] = 0.5 * mala_clip(eps * f, c[j]);
+    }
+}
+
+template <bool DEVICE_NOISE, bool RECORD>
+__global__ __launch_bounds__(kWaveLanes * kWaveChainsPerBlock) void lv_hmc_metric_wave_kernel(LvHmcMetricArgs a) {
+    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x / kWaveLanes));
+    const int lane = (int)(threadIdx.x % kWaveLanes);
+    const int64_t i = (int64_t)blockIdx.x * kWaveChainsPerBlock + wave;
+    if (i >= a.chains) return;            // the whole wave (partial last block)
+    double* st = a.state + kHmcMetricStateWords * i;
+    int64_t* sti = reinterpret_cast<int64_t*>(st);
+    double x[4], g[4], lp;
+    {
+        const double2* s2 = reinterpret_cast<const double2*>(st);
+        const double2 s0 = s2[0], s1 = s2[1], g0 = s2[4], g1 = s2[5];
+        x[0] = s0.x; x[1] = s0.y; x[2] = s1.x; x[3] = s1.y;
+        g[0] = g0.x; g[1] = g0.y; g[2] = g1.x; g[3] = g1.y;
+    }
+    lp = st[4];
+    int64_t accepted = sti[5], failed = sti[6];
+    double eps = a.adapt ? st[16] : a.eps_chain[i];
+    const double* lam = a.metric_chol + 10 * i;
+    double* rows = a.samples + (i * a.out_ld + a.out_row0) * 4;
+    double* grads = a.grad + (i * a.out_ld + a.out_row0) * 4;
+    double* lps = a.log_p + i * a.out_ld + a.out_row0;
+    double* alphas = a.accept_stat + i * a.out_ld + a.out_row0;
+    double* epss = a.step_size + i * a.out_ld + a.out_row0;
+    double* zs = nullptr;
+    double* lus = nullptr;
+    if (!DEVICE_NOISE || RECORD) {
+        zs = a.z + (i * a.noise_ld + a.noise_row0) * 4;
+        lus = a.log_u + i * a.noise_ld + a.noise_row0;
+    }
+    const uint64_t chain = (uint64_t)(a.first_chain + i);
+    // the trajectory: its current point q with g(q), its momentum r, K(r^0) and the step's log_u
+    double q[4], gq[4], r[4] = {0.0, 0.0, 0.0, 0.0}, k0 = 0.0, log_u = 0.0;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) { q[j] = x[j]; gq[j] = g[j]; }
+    int l = 0;                            // stages of step k done
+    // k = -1: the start row itself (a.init), evaluated by the same code as every stage
+#pragma unroll 1
+    for (int64_t k = a.init ? -1 : 0; k < a.steps;) {
+        const bool start = k < 0;
+        if (!start && l == 0) {
+            if constexpr (DEVICE_NOISE) {
+                device_noise(a.seed, chain, (uint64_t)(a.first_step + k), r, log_u);
+                if constexpr (RECORD) {
+                    if (lane == 0) {
+                        reinterpret_cast<double2*>(zs + 4 * k)[0] = make_double2(r[0], r[1]);
+                        reinterpret_cast<double2*>(zs + 4 * k)[1] = make_double2(r[2], r[3]);
+                        lus[k] = log_u;
+                    }
+                }
+            } else {
+                const double2 z01 = reinterpret_cast<const double2*>(zs + 4 * k)[0];
+                const double2 z23 = reinterpret_cast<const double2*>(zs + 4 * k)[1];
+                r[0] = z01.x; r[1] = z01.y; r[2] = z23.x; r[3] = z23.y;
+                log_u = lus[k];
+            }
+            double s = 0.0;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) s += r[j] * r[j];
+            k0 = 0.5 * s;
+        }
+        double rp[4], p[4], th[4];
+        bool ok = true;
+        {
+            double hk[4];
+            metric_half_kick(lam, gq, eps, a.clip, hk);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) rp[j] = r[j] + hk[j];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                double v = lam[j * (j + 1) / 2] * rp[0];
+#pragma unroll
+                for (int kk = 1; kk <= j; ++kk) v += lam[j * (j + 1) / 2 + kk] * rp[kk];
+                p[j] = start ? q[j] : q[j] + eps * v;
+                th[j] = exp(p[j]);
+                ok = ok && isfinite(th[j]) && th[j] != 0.0;
+            }
+        }
+        double ll = 0.0, acc[4] = {0.0, 0.0, 0.0, 0.0};     // this lane's terms, in increasing k
+        int status = 0;
+        if (ok) {
+            int kq = lane;
+            double tq = lane < a.p.t_n ? a.p.t_eval[lane] : 0.0;
+            status = lv_integrate<10>(th, a.p, [&](double t_old, double t_new, double inv_hd, const double* y,
+                                                   const double (*Q)[rk45::kDenseOrder], bool last) {
+                lv_observe_strided<10>(a.p, kq, tq, kWaveLanes, t_old, t_new, inv_hd, y, Q, last,
+                                       [&](int kk, const double* u) {
+                                           ll += lv_loglik_term(a.p, kk, u);
+                                           lv_grad_term(a.p, a.cinv, kk, u, acc);
+                                       });
+                return 0;
+            });
+        }
+        // a compiler barrier (no instruction): Lam is loaded again below instead of being held in 24 further
+        // registers across the integration
+        asm volatile("" ::: "memory");
+#pragma unroll
+        for (int off = kWaveLanes / 2; off >= 1; off >>= 1) {
+            ll += __shfl_xor(ll, off);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) acc[j] += __shfl_xor(acc[j], off);
+        }
+        double lp_new = NAN, g_new[4] = {NAN, NAN, NAN, NAN};   // theta out of range, or the integration failed
+        if (ok && status == 0) {
+            lp_new = wave_first(ll) + lv_log_prior(p, a.p.norm_logc);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) g_new[j] = th[j] * wave_first(acc[j]) - p[j];
+        }
+        if (start) {
+            lp = lp_new;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) g[j] = g_new[j];
+        } else {
+            double hk[4];
+            metric_half_kick(lam, g_new, eps, a.clip, hk);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                r[j] = rp[j] + hk[j];
+                q[j] = p[j];
+                gq[j] = g_new[j];
+            }
+            if (++l < a.n_leapfrog) continue;
+            // the trajectory's end: a failed stage has made every later lp NaN
+            if (!(lp_new == lp_new)) ++failed;
+            double s = 0.0;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) s += r[j] * r[j];
+            const double da = (lp_new - lp) + (k0 - 0.5 * s);
+            if (log_u < da) {
+#pragma unroll
+                for (int j = 0; j < 4; ++j) { x[j] = q[j]; g[j] = gq[j]; }
+                lp = lp_new;
+                ++accepted;
+            }
+            const double ea = exp(da);
+            const double alpha = da == da ? (ea < 1.0 ? ea : 1.0) : 0.0;
+            if (lane == 0) {
+                alphas[k] = alpha;
+                epss[k] = eps;
+            }
+            if (a.adapt) {
+                const double m = st[17] + 1.0, eta = 1.0 / (m + kDaT0);
+                const double sbar = (1.0 - eta) * st[18] + eta * (a.delta - alpha);
+                const double ell = st[20] - (sbar * sqrt(m)) / kDaGamma;
+                const double w = pow(m, -kDaKappa);
+                const double xbar = (1.0 - w) * st[19] + w * ell;
+                eps = exp(ell);
+                st[16] = eps;             // every lane: the same bits (above)
+                st[17] = m;
+                st[18] = sbar;
+                st[19] = xbar;
+            }
+        }
+        if (lane == 0) {
+            reinterpret_cast<double2*>(rows + 4 * k)[0] = make_double2(x[0], x[1]);
+            reinterpret_cast<double2*>(rows + 4 * k)[1] = make_double2(x[2], x[3]);
+            reinterpret_cast<double2*>(grads + 4 * k)[0] = make_double2(g[0], g[1]);
+            reinterpret_cast<double2*>(grads + 4 * k)[1] = make_double2(g[2], g[3]);
+            lps[k] = lp;
+        }
+#pragma unroll
+        for (int j = 0; j < 4; ++j) { q[j] = x[j]; gq[j] = g[j]; }
+        l = 0;
+        ++k;
+    }
+    if (lane == 0) {
+        double2* s2 = reinterpret_cast<double2*>(st);
+        s2[0] = make_double2(x[0], x[1]);
+        s2[1] = make_double2(x[2], x[3]);
+        s2[4] = make_double2(g[0], g[1]);
+        s2[5] = make_double2(g[2], g[3]);
+        st[4] = lp;
+        sti[5] = accepted;
+        sti[6] = failed;
+    }
+}
+
 // kernel[noise_mode] (supplied, Philox, Philox + record) over a.chains chains, chains_per_block to a block
 template <class Args>
 hipError_t launch_noise_mode(void (*const (&kernel)[3])(Args), const Args& a, int chains_per_block,
@@ -634,6 +846,13 @@ hipError_t launch_lv_mala_wave(const LvMalaArgs& a, hipStream_t s) {
 hipError_t launch_lv_hmc_wave(const LvHmcArgs& a, hipStream_t s) {
     return launch_noise_mode<LvHmcArgs>({lv_hmc_wave_kernel<false, false>, lv_hmc_wave_kernel<true, false>,
                                          lv_hmc_wave_kernel<true, true>}, a, kWaveChainsPerBlock, kWaveThreads, s);
+}
+
+hipError_t launch_lv_hmc_metric_wave(const LvHmcMetricArgs& a, hipStream_t s) {
+    return launch_noise_mode<LvHmcMetricArgs>({lv_hmc_metric_wave_kernel<false, false>,
+                                               lv_hmc_metric_wave_kernel<true, false>,
+                                               lv_hmc_metric_wave_kernel<true, true>}, a, kWaveChainsPerBlock,
+                                              kWaveThreads, s);
 }
 
 hipError_t launch_lv_rwmh_wave(const LvMcmcArgs& a, hipStream_t s) {

@@ -272,6 +272,37 @@ struct LvHmcArgs {
 };
 hipError_t launch_lv_hmc_wave(const LvHmcArgs& a, hipStream_t s);
 
+// HMC with a per-chain step size, a per-chain dense metric and step-size adaptation, one wave per chain
+// (csrc/lv_mcmc.hip: lv_hmc_metric_wave_kernel); the fields it shares with LvHmcArgs mean the same
+struct LvHmcMetricArgs {
+    double* state;            // (chains, 24) words: LvMalaArgs' 16, then eps, m, sbar, xbar, mu, 3 spare
+    int64_t chains;
+    int64_t first_chain;
+    int64_t first_step;
+    int64_t steps;
+    int init;
+    const double* eps_chain;  // (chains): the step size of every chain (adapt = 0)
+    const double* metric_chol;    // (chains, 10): packed row-major lower triangle of Lam, M^-1 = Lam Lam^T
+    double clip[4];
+    int n_leapfrog;
+    int adapt;                // 1: eps from the state record, dual averaging after every step
+    double delta;             // dual averaging's target acceptance, in (0, 1)
+    int noise_mode;
+    uint64_t seed;
+    double* z;
+    double* log_u;
+    int64_t noise_ld, noise_row0;
+    LvProblem p;
+    double cinv[4];
+    double* samples;          // (chains, out_ld, 4)
+    double* log_p;            // (chains, out_ld)
+    double* grad;             // (chains, out_ld, 4)
+    double* accept_stat;      // (chains, out_ld): min(1, exp(a)) of the step that wrote the row
+    double* step_size;        // (chains, out_ld): the eps that step used
+    int64_t out_ld, out_row0;
+};
+hipError_t launch_lv_hmc_metric_wave(const LvHmcMetricArgs& a, hipStream_t s);
+
 hipError_t launch_greedy_rank_exchange(const double* recs, int K, int64_t stride, int d,
                                        const MailboxPeers& peers, int rank, int nranks, int64_t t,
                                        double* recv, unsigned* status, hipStream_t s);

@@ -118,6 +118,13 @@ SIGNATURES = {
     'st_lv_hmc_wave': (ctypes.c_int, [_c_dp, _i64, _i64, _i64, _i64, _i32, _c_dp, _c_dp, _i32, _i32, ctypes.c_uint64,
                                       _c_dp, _c_dp, _i64, _i64, _c_dp, _i32, _c_dp, _c_dp, _c_dp, _f64, _f64,
                                       _c_dp, _i64, _c_dp, _c_dp, _c_dp, _i64, _i64, _c_dp]),
+    'st_lv_hmc_metric_workspace_bytes': (_i64, [_i64]),
+    # eps_chain, metric_chol, accept_stat, step_size: device arrays; kick_clip, span_u0_tol, whiten, cov_inv: host
+    # arrays; adapt: 0 / 1; delta: double; seed: uint64
+    'st_lv_hmc_metric_wave': (ctypes.c_int, [_c_dp, _i64, _i64, _i64, _i64, _i32, _c_dp, _c_dp, _c_dp, _i32, _i32, _f64,
+                                             _i32, ctypes.c_uint64, _c_dp, _c_dp, _i64, _i64, _c_dp, _i32, _c_dp, _c_dp,
+                                             _c_dp, _f64, _f64, _c_dp, _i64, _c_dp, _c_dp, _c_dp, _c_dp, _c_dp, _i64,
+                                             _i64, _c_dp]),
     'st_kde_workspace_bytes': (_i64, [_i64, _i32]),
     'st_kde_logpdf_grad': (ctypes.c_int, [_c_dp, _i64, _i64, _c_dp, _f64, _c_dp, _i64, _i64, _i32, _f64, _c_dp,
                                           _c_dp, _c_dp, _c_dp, _i64, _c_dp]),

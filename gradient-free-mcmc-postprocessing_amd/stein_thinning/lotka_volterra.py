@@ -277,13 +277,27 @@ def _chain_problem(data, rtol, atol):
     return (data, t, y, s) + _density_constants(data)
 
 
+def _check_start(failed_start, log_p):
+    """Raise for chains whose start row has no density (its log_p is NaN)."""
+    import torch
+    bad = torch.isnan(log_p[:, 0])
+    if bool(bad.any()):
+        first = int(torch.nonzero(bad)[0, 0])
+        raise ValueError(f'{failed_start} of {int(bad.sum())} starting point(s) failed '
+                         f'(first: chain {first}): theta out of range or the RK45 integration did not finish')
+
+
 def _run_chains(*, failed_start, x0, n_samples, seed, noise, first_chain, spl, max_steps, problem, return_noise,
-                device_out, state_words, n_extra, launch):
+                device_out, state_words, n_extra, launch, n_extra_rows=0, drive=None):
     """Run checked chains (``_chain_start``, ``_chain_noise``, ``_chain_problem``) on the device: returns samples,
-    log_p, ``n_extra`` further (chains, n_samples, 4) per-row outputs, accepted, n_failed, z, log_u.  The state
+    log_p, ``n_extra`` further (chains, n_samples, 4) per-row outputs, ``n_extra_rows`` further (chains, n_samples)
+    ones, accepted, n_failed, z, log_u.  The state
     record has ``state_words`` words per chain.  ``launch(L, head=, mid=, rows=, extra=, tail=)`` makes one
     entry-point call from the argument groups that every sampler's entry point has, in this order, between its own
-    (head: state .. init; mid: noise_mode .. norm_logc; rows: max_steps, samples, log_p; tail: out_ld ..)."""
+    (head: state .. init; mid: noise_mode .. norm_logc; rows: max_steps, samples, log_p; tail: out_ld ..).
+    ``drive(advance, state, samples, log_p)`` replaces the plain run of all steps: it calls ``advance(k0, k1)`` for
+    consecutive step ranges (launches never cross a range's end; ``each=`` is called after every launch) and may read
+    and write the state record and whatever device arrays ``launch`` hands over in between."""
     import torch
     _, t, y, s, U, c_log, norm_logc = problem
     chains, steps = x0.shape[0], n_samples - 1
@@ -296,6 +310,7 @@ def _run_chains(*, failed_start, x0, n_samples, seed, noise, first_chain, spl, m
     ld = max(n_samples, 2)
     samples, *extra = (torch.empty((chains, ld, 4), dtype=torch.float64, device=dev) for _ in range(1 + n_extra))
     log_p = torch.empty((chains, ld), dtype=torch.float64, device=dev)
+    extra += [torch.empty((chains, ld), dtype=torch.float64, device=dev) for _ in range(n_extra_rows)]
     mode, zd, lud = 1, None, None
     if steps >= 1 and noise is not None:
         mode = 0
@@ -306,18 +321,22 @@ def _run_chains(*, failed_start, x0, n_samples, seed, noise, first_chain, spl, m
         zd = torch.empty((chains, steps, 4), dtype=torch.float64, device=dev)
         lud = torch.empty((chains, steps), dtype=torch.float64, device=dev)
     run = max(steps, 1)
-    for k0 in range(0, run, spl):
-        k = min(spl, run - k0)
-        launch(L, head=(nat.ptr(state), chains, int(first_chain), k0 + 1, k, 1 if k0 == 0 else 0),
-               mid=(mode, seed if noise is None else 0, nat.ptr(zd), nat.ptr(lud), run, k0, nat.ptr(td), t.size,
-                    nat.ptr(yd), s.ctypes.data, U.ctypes.data, c_log, norm_logc),
-               rows=(int(max_steps), nat.ptr(samples), nat.ptr(log_p)), extra=[nat.ptr(e) for e in extra],
-               tail=(ld, k0 + 1, nat.stream_handle()))
-    bad = torch.isnan(log_p[:, 0])
-    if bool(bad.any()):
-        first = int(torch.nonzero(bad)[0, 0])
-        raise ValueError(f'{failed_start} of {int(bad.sum())} starting point(s) failed '
-                         f'(first: chain {first}): theta out of range or the RK45 integration did not finish')
+
+    def advance(first, last, each=None):
+        for k0 in range(first, last, spl):
+            k = min(spl, last - k0)
+            launch(L, head=(nat.ptr(state), chains, int(first_chain), k0 + 1, k, 1 if k0 == 0 else 0),
+                   mid=(mode, seed if noise is None else 0, nat.ptr(zd), nat.ptr(lud), run, k0, nat.ptr(td), t.size,
+                        nat.ptr(yd), s.ctypes.data, U.ctypes.data, c_log, norm_logc),
+                   rows=(int(max_steps), nat.ptr(samples), nat.ptr(log_p)), extra=[nat.ptr(e) for e in extra],
+                   tail=(ld, k0 + 1, nat.stream_handle()))
+            if each is not None:
+                each()
+    if drive is None:
+        advance(0, run)
+    else:
+        drive(advance, state, samples, log_p)
+    _check_start(failed_start, log_p)
     counts = state.view(torch.int64)[:, 5:7]
     if steps == 0:
         counts = torch.zeros_like(counts)
@@ -557,3 +576,342 @@ def hmc_sample(log_theta_init, n_samples, step_size, n_leapfrog, *, seed=None, n
         failed_start='hmc_sample: the evaluation', x0=x0, n_samples=n_samples, seed=seed, noise=noise,
         first_chain=first_chain, spl=spl, max_steps=max_steps, problem=problem, return_noise=return_noise,
         device_out=device_out, state_words=16, n_extra=1, launch=launch))
+
+
+# ---- HMC with a per-chain step size and dense metric, and its warm-up ----
+# words 16 .. 20 of st_lv_hmc_metric_wave's state record: eps, m, sbar, xbar, mu
+_DA_WORDS = slice(16, 21)
+DA_GAMMA, DA_T0, DA_KAPPA = 0.05, 10.0, 0.75        # the kernel's constants (Stan's defaults)
+WARMUP_INIT_BUFFER, WARMUP_TERM_BUFFER, WARMUP_BASE_WINDOW = 75, 50, 25
+METRIC_REG = 1e-3                                    # Stan's regulariser: Sigma = n/(n+5) S + 1e-3 * 5/(n+5) I
+
+
+@dataclass
+class HmcMetricSample:
+    """Result of ``hmc_metric_sample``: ``HmcSample``'s fields, then the per-step outputs."""
+    samples: object
+    log_p: object
+    grad: object
+    accepted: object
+    n_failed: object
+    z: object = None
+    log_u: object = None
+    accept_stat: object = None        # (chains, n_samples - 1): min(1, exp(a)) of the step that wrote row t + 1
+    step_size: object = None          # (chains, n_samples - 1): the eps that step used
+    adapt_state: object = None        # (chains, 5) eps, m, sbar, xbar, mu after the last step (target_accept given)
+    adapt_trace: object = None        # (launches, chains, 5): the same after every launch (return_adapt_trace)
+
+
+@dataclass
+class HmcWindow:
+    """One slow window of ``hmc_warmup``: steps [start, stop), the dual-averaging xbar (chains,) at its end, and the
+    step size (chains,) and metric factor (chains, 4, 4) the chains went on with."""
+    start: int
+    stop: int
+    xbar: object
+    step_size: object
+    metric_chol: object
+
+
+@dataclass
+class HmcAdaptation:
+    """Result of ``hmc_warmup`` (NumPy arrays, or ROCm tensors with ``device_out=True`` for the per-row fields)."""
+    step_size: object                 # (chains,) the adapted eps = exp(xbar)
+    metric_chol: object               # (chains, 4, 4) Lam, lower triangular, M^-1 = Lam Lam^T
+    last_row: object                  # (chains, 4) the last warm-up row: the start of the sampling run
+    samples: object                   # (chains, n_warmup + 1, 4); row 0 is the start
+    log_p: object
+    grad: object
+    accept_stat: object               # (chains, n_warmup)
+    step_sizes: object                # (chains, n_warmup): the eps every warm-up step used
+    windows: object                   # list of HmcWindow
+    accepted: object = None
+    n_failed: object = None
+
+
+def _libm(fn, a, *args):
+    """``fn`` (a ``math`` function) of every element of ``a``, one C-library call per value.  The warm-up's few host
+    scalars go this way, not through NumPy's exp / log / power, whose SIMD variants differ by an ulp between CPUs: the
+    chains are chaotic, and the schedule should give the same step sizes wherever it runs."""
+    a = np.asarray(a, dtype=np.float64)
+
+    def one(v):
+        try:
+            return fn(v, *args)
+        except OverflowError:
+            return math.inf
+    return np.array([one(float(v)) for v in a.ravel()], dtype=np.float64).reshape(a.shape)
+
+
+def hmc_warmup_windows(n_warmup: int):
+    """The slow windows [(start, stop), ...] of Stan's warm-up schedule for ``n_warmup`` steps: an initial buffer of
+    75 steps, a final one of 50 and a first window of 25 -- or, where these do not fit, 15 % / 10 % of ``n_warmup``
+    (rounded down) and the rest as one window; every window is twice as long as the one before, and a window is
+    stretched to the end of the slow region when the next one would not fit.  Steps before the first window and
+    after the last adapt the step size only."""
+    if isinstance(n_warmup, bool) or int(n_warmup) != n_warmup or n_warmup < 20:
+        raise ValueError(f'n_warmup must be an integer >= 20, got {n_warmup!r}')
+    n = int(n_warmup)
+    init, term, size = WARMUP_INIT_BUFFER, WARMUP_TERM_BUFFER, WARMUP_BASE_WINDOW
+    if init + size + term > n:
+        init, term = int(0.15 * n), int(0.1 * n)
+        size = n - init - term
+    slow_end = n - term
+    windows, start = [], init
+    while start < slow_end:
+        stop = start + size
+        if stop + 2 * size > slow_end:
+            stop = slow_end
+        windows.append((start, stop))
+        start, size = stop, 2 * size
+    return windows
+
+
+def hmc_window_metric(rows):
+    """Lam (chains, 4, 4) from a window's rows (chains, n, 4), n >= 2: S the sample covariance (n - 1 divisor),
+    Sigma = n / (n + 5) S + 1e-3 * 5 / (n + 5) I (Stan's regularisation), Lam = chol(Sigma), lower triangular.  torch,
+    batched over the chains, on the rows' device; NumPy in, NumPy out."""
+    import torch
+    r = rows if _is_tensor(rows) else torch.from_numpy(np.asarray(rows, dtype=np.float64))
+    if r.ndim != 3 or r.shape[2] != 4 or r.shape[1] < 2:
+        raise ValueError(f'rows must be (chains, n >= 2, 4), got {tuple(r.shape)}')
+    n = r.shape[1]
+    d = r - r.mean(dim=1, keepdim=True)
+    cov = d.transpose(1, 2) @ d / (n - 1)
+    sigma = (n / (n + 5.0)) * cov + (METRIC_REG * 5.0 / (n + 5.0)) * torch.eye(4, dtype=r.dtype, device=r.device)
+    lam = torch.linalg.cholesky(sigma)
+    return lam if _is_tensor(rows) else lam.numpy()
+
+
+def hmc_rescale_step(step_size, chol_old, chol_new):
+    """The step size after a change of metric: eps * (det Lam_old / det Lam_new) ** (1 / 4), per chain -- the
+    project's own rule, which keeps the mean physical step eps * det(Lam) ** (1 / 4) across the change."""
+    old, new = (np.asarray(a.cpu().numpy() if _is_tensor(a) else a, dtype=np.float64) for a in (chol_old, chol_new))
+    det_old, det_new = (((a[..., 0, 0] * a[..., 1, 1]) * a[..., 2, 2]) * a[..., 3, 3] for a in (old, new))
+    return np.asarray(step_size, dtype=np.float64) * _libm(math.pow, det_old / det_new, 0.25)
+
+
+def hmc_adapt_restart(step_size):
+    """The dual-averaging state (chains, 5) = eps, m, sbar, xbar, mu that starts an adaptation at eps: m = sbar =
+    xbar = 0, mu = log(10 eps)."""
+    eps = np.atleast_1d(np.asarray(step_size, dtype=np.float64))
+    da = np.zeros((eps.size, 5))
+    da[:, 0] = eps
+    da[:, 4] = _libm(math.log, 10.0 * eps)
+    return da
+
+
+def hmc_warmup_schedule(run_segment, n_warmup, step_size, metric_chol, window_metric=None):
+    """The host side of ``hmc_warmup``, without a device: ``run_segment(start, stop, metric_chol, da)`` runs steps
+    [start, stop) of all chains with the metric factors (chains, 4, 4) from the dual-averaging state ``da`` (chains, 5)
+    = eps, m, sbar, xbar, mu, adapting eps after every step, and returns (the rows these steps wrote (chains,
+    stop - start, 4), the state after them).  Segments are the initial buffer, every slow window of
+    ``hmc_warmup_windows`` and the final buffer.  At a slow window's end, per chain: Lam_new =
+    ``hmc_window_metric(rows)``, eps = ``hmc_rescale_step(exp(xbar), Lam_old, Lam_new)`` and the adaptation restarts
+    (``hmc_adapt_restart``).  At the end eps = exp(xbar).  ``window_metric`` replaces ``hmc_window_metric`` (a test double's
+    own, bit-reproducible statement of it).  Returns (eps (chains,), Lam (chains, 4, 4), [HmcWindow])."""
+    windows = hmc_warmup_windows(n_warmup)
+    chol = np.array(metric_chol, dtype=np.float64)
+    da = hmc_adapt_restart(np.broadcast_to(np.asarray(step_size, dtype=np.float64), chol.shape[:1]))
+    segments =[(0, windows[0][0], False)] + [(a, b, True) for a, b in windows] + [(windows[-1][1], int(n_warmup), False)]
+    trace = []
+    for start, stop, slow in segments:
+        if stop == start:
+            continue
+        rows, da = run_segment(start, stop, chol, da)
+        da = np.array(da, dtype=np.float64)
+        if slow:
+            new = (window_metric or hmc_window_metric)(rows)
+            new = np.array(new.cpu().numpy() if _is_tensor(new) else new, dtype=np.float64)
+            eps = hmc_rescale_step(_libm(math.exp, da[:, 3]), chol, new)
+            trace.append(HmcWindow(start, stop, da[:, 3].copy(), eps, new))
+            chol, da = new, hmc_adapt_restart(eps)
+    return _libm(math.exp, da[:, 3]), chol, trace
+
+
+def _metric_chol(metric_chol, chains):
+    """Checked (chains, 4, 4) lower-triangular factors with a positive diagonal."""
+    lam = np.array(metric_chol.cpu().numpy() if _is_tensor(metric_chol) else metric_chol, dtype=np.float64)
+    if lam.shape == (4, 4):
+        lam = np.tile(lam, (chains, 1, 1))
+    if lam.shape != (chains, 4, 4):
+        raise ValueError(f'metric_chol must be (4, 4) or ({chains}, 4, 4), got {lam.shape}')
+    if not np.all(np.isfinite(lam)):
+        raise ValueError('metric_chol must be finite')
+    if np.any(np.triu(lam, 1) != 0.0):
+        raise ValueError('metric_chol must be lower triangular')
+    if np.any(np.diagonal(lam, axis1=1, axis2=2) <= 0.0):
+        raise ValueError('metric_chol must have a positive diagonal')
+    return lam
+
+
+_TRIL = np.tril_indices(4)            # row-major order of the lower triangle: the kernel's packing
+
+
+def _hmc_metric_run(who, log_theta_init, n_samples, step_size, metric_chol, n_leapfrog, *, seed, noise, kick_cap, data,
+                    rtol, atol, max_steps, first_chain, steps_per_launch, return_noise, device_out, delta, drive_with):
+    """The checks and the launch closure ``hmc_metric_sample`` and ``hmc_warmup`` share.  ``drive_with(eps_d, chol_d)``
+    returns ``_run_chains``' drive (or None) given the device arrays the launches read."""
+    import torch
+    x0, n_samples, _ = _chain_start(log_theta_init, n_samples, 1.0)
+    chains = x0.shape[0]
+    eps = np.asarray(step_size.cpu().numpy() if _is_tensor(step_size) else step_size, dtype=np.float64)
+    if eps.ndim == 0:
+        eps = np.full(chains, float(eps))
+    if eps.shape != (chains,):
+        raise ValueError(f'step_size must be a scalar or ({chains},), one per chain, got {eps.shape}')
+    if not np.all(np.isfinite(eps)) or np.any(eps <= 0):
+        raise ValueError(f'step_size must be finite and > 0, got {step_size!r}')
+    lam = _metric_chol(metric_chol, chains)
+    if isinstance(n_leapfrog, bool) or not isinstance(n_leapfrog, (int, np.integer)) or not 1 <= n_leapfrog < 2 ** 31:
+        raise ValueError(f'n_leapfrog must be an integer >= 1, got {n_leapfrog!r}')
+    n_leapfrog = int(n_leapfrog)
+    try:
+        cap = float(kick_cap)
+    except (TypeError, ValueError):
+        raise ValueError(f'kick_cap must be a number > 0, got {kick_cap!r}') from None
+    if isinstance(kick_cap, bool) or not cap > 0:
+        raise ValueError(f'kick_cap must be > 0 (inf: no cap), got {kick_cap!r}')
+    adapt = delta is not None
+    if adapt and not 0.0 < float(delta) < 1.0:
+        raise ValueError(f'target_accept must lie in (0, 1), got {delta!r}')
+    clip = np.full(4, cap)
+    seed, noise, spl = _chain_noise(chains, n_samples - 1, seed, noise, first_chain, steps_per_launch,
+                                    STEPS_PER_LAUNCH_HMC(n_leapfrog), max_steps)
+    problem = _chain_problem(data, rtol, atol)
+    cinv = np.ascontiguousarray(np.linalg.inv(np.asarray(problem[0].cov, dtype=np.float64)))
+    dev = nat.require_device()
+    eps_d = torch.from_numpy(np.ascontiguousarray(eps)).to(dev)
+    chol_d = torch.from_numpy(np.ascontiguousarray(lam[:, _TRIL[0], _TRIL[1]])).to(dev)
+
+    def launch(L, head, mid, rows, extra, tail):
+        nat.check(L.st_lv_hmc_metric_wave(*head, nat.ptr(eps_d), nat.ptr(chol_d), clip.ctypes.data, n_leapfrog,
+                                          1 if adapt else 0, float(delta) if adapt else 0.5, *mid, cinv.ctypes.data,
+                                          *rows, *extra, *tail), 'st_lv_hmc_metric_wave')
+    res = _run_chains(
+        failed_start=f'{who}: the evaluation', x0=x0, n_samples=n_samples, seed=seed, noise=noise,
+        first_chain=first_chain, spl=spl, max_steps=max_steps, problem=problem, return_noise=return_noise,
+        device_out=device_out, state_words=24, n_extra=1, launch=launch, n_extra_rows=2,
+        drive=drive_with(eps_d, chol_d, eps, lam))
+    samples, log_p, grad, alpha, eps_used, accepted, n_failed, z, log_u = res
+    return HmcMetricSample(samples, log_p, grad, accepted, n_failed, z, log_u, alpha[:, 1:], eps_used[:, 1:])
+
+
+def hmc_metric_sample(log_theta_init, n_samples, step_size, metric_chol, n_leapfrog, *, seed=None, noise=None,
+                      kick_cap: float = math.inf, target_accept: Optional[float] = None, adapt_state=None,
+                      return_adapt_trace: bool = False, data: Optional[LvData] = None, rtol: float = RTOL,
+                      atol: float = ATOL, max_steps: int = MAX_STEPS, first_chain: int = 0,
+                      steps_per_launch: Optional[int] = None, return_noise: bool = False,
+                      device_out: bool = False) -> HmcMetricSample:
+    """HMC chains on the LV log posterior with a step size per chain and a dense metric per chain, one chain per GPU
+    wave (``st_lv_hmc_metric_wave``, csrc/lv_mcmc.hip): ``hmc_sample`` as Stan's adapted sampler would run it after
+    ``hmc_warmup``.  This is the project's own definition; Stan's bits are not claimed, and there is neither NUTS nor
+    a jittered trajectory length.
+
+    Definition.  ``step_size`` is eps, a scalar or (chains,) -- one per CHAIN, not per component as in ``hmc_sample``;
+    ``metric_chol`` is Lam, (4, 4) or (chains, 4, 4), lower triangular with a positive diagonal (anything else raises
+    ValueError), the inverse metric being M^-1 = Lam Lam^T.  The momentum stays r ~ N(0, I), so the noise is
+    ``rw_sample``'s bit for bit and K(r) = 0.5 * sum_j r_j r_j.  With f_j(q) = Lam_jj g_j(q) + sum_{k > j} Lam_kj g_k(q)
+    (the first term alone, then k ascending), hk(q) = 0.5 * clip(eps * f(q), -c, c) and v_j = sum_{k <= j} Lam_jk r'_k
+    (from the k = 0 term, k ascending) a stage is ``r' = r + hk(q); q = q + eps * v; r = r' + hk(q)``: unit-mass HMC in
+    y = Lam^-1 x.  The capped force depends on q alone, so every stage stays a shear and the chain still targets the
+    posterior.  Accept, failure and NaN rules, ``n_leapfrog``, ``kick_cap`` and every other keyword are
+    ``hmc_sample``'s.  With Lam = I and a scalar eps the result is ``hmc_sample``'s bit for bit.
+
+    Two per-step outputs: ``accept_stat`` = min(1, exp(a)) with a = (lp(q^L) - lp(x)) + (K(r^0) - K(r^L)), 0 when a is
+    NaN, and ``step_size`` = the eps the step used; entry t belongs to the step that wrote row t + 1.
+
+    ``target_accept`` = delta in (0, 1) turns on the kernel's dual averaging of eps (Hoffman & Gelman; Stan's
+    constants gamma 0.05, t0 10, kappa 0.75): after every step m += 1; eta = 1 / (m + 10); sbar = (1 - eta) sbar +
+    eta (delta - alpha); ell = mu - sbar sqrt(m) / gamma; w = m ** -0.75; xbar = (1 - w) xbar + w ell; eps = exp(ell).
+    ``adapt_state`` (chains, 5) = eps, m, sbar, xbar, mu is the state it starts from (default:
+    ``hmc_adapt_restart(step_size)``, i.e. mu = log(10 eps)); the result's ``adapt_state`` is the state after the last
+    step and, with ``return_adapt_trace``, ``adapt_trace`` the state after every launch.  The state lives in the
+    chain's state record, so the result does not depend on ``steps_per_launch`` (default
+    ``STEPS_PER_LAUNCH_HMC(n_leapfrog)``); a chain is bit-identical to itself under any launch split, any
+    ``first_chain`` offset, with or without ``return_noise``, and when re-run from its recorded noise."""
+    import torch
+    out = {}
+
+    def drive_with(eps_d, chol_d, eps, lam):
+        if target_accept is None:
+            if adapt_state is not None or return_adapt_trace:
+                raise ValueError('adapt_state and return_adapt_trace need target_accept')
+            return None
+        da0 = hmc_adapt_restart(eps) if adapt_state is None else np.array(adapt_state, dtype=np.float64)
+        if da0.shape != (eps.size, 5) or not np.all(np.isfinite(da0)) or np.any(da0[:, 0] <= 0) or np.any(da0[:, 1] < 0):
+            raise ValueError(f'adapt_state must be ({eps.size}, 5) finite values eps > 0, m >= 0, sbar, xbar, mu')
+
+        def drive(advance, state, samples, log_p):
+            state[:, _DA_WORDS] = torch.from_numpy(da0).to(state.device)
+            trace = []
+            advance(0, samples.shape[1] - 1,
+                    each=(lambda: trace.append(state[:, _DA_WORDS].clone())) if return_adapt_trace else None)
+            out['state'] = state[:, _DA_WORDS].clone()
+            if samples.shape[1] - 1 > int(n_samples) - 1:       # a one-row run: its spare step is dropped
+                out['state'], trace = torch.from_numpy(da0).to(state.device), trace[:0]
+            out['trace'] = (torch.stack(trace) if trace else state.new_empty((0, eps.size, 5))) \
+                if return_adapt_trace else None
+        return drive
+    run = _hmc_metric_run('hmc_metric_sample', log_theta_init, n_samples, step_size, metric_chol, n_leapfrog, seed=seed,
+                          noise=noise, kick_cap=kick_cap, data=data, rtol=rtol, atol=atol, max_steps=max_steps,
+                          first_chain=first_chain, steps_per_launch=steps_per_launch, return_noise=return_noise,
+                          device_out=device_out, delta=target_accept, drive_with=drive_with)
+    if target_accept is not None:
+        run.adapt_state = out['state'] if device_out else out['state'].cpu().numpy()
+        if out['trace'] is not None:
+            run.adapt_trace = out['trace'] if device_out else out['trace'].cpu().numpy()
+    return run
+
+
+def hmc_warmup(log_theta_init, n_warmup, step_size, n_leapfrog, *, target_accept: float = 0.8, metric_chol=None,
+               seed=None, noise=None, kick_cap: float = math.inf, data: Optional[LvData] = None, rtol: float = RTOL,
+               atol: float = ATOL, max_steps: int = MAX_STEPS, first_chain: int = 0,
+               steps_per_launch: Optional[int] = None, device_out: bool = False) -> HmcAdaptation:
+    """Warm-up for ``hmc_metric_sample``: ``n_warmup`` HMC steps per chain during which the step size is tuned to the
+    acceptance ``target_accept`` by dual averaging inside the kernel and a dense metric is learned from the draws in
+    windows.  It follows Stan's warm-up -- Hoffman & Gelman's dual averaging, Stan's windows and its regularisation of
+    the covariance -- but these are this project's own definitions and Stan's bits are not claimed; NUTS, jittered
+    trajectory lengths and Stan's search for a first step size are out of scope.
+
+    Schedule (``hmc_warmup_windows``): 75 steps that adapt eps only, slow windows of 25, 50, 100, ... steps (the last
+    stretched to the end of the slow region), 50 final steps that adapt eps only; 15 % / 10 % / one window where
+    these do not fit; ``n_warmup`` < 20 raises ValueError.  The chains start from ``step_size`` (a scalar or
+    (chains,)) and ``metric_chol`` (default: the identity) with mu = log(10 eps), m = sbar = xbar = 0.  At each slow
+    window's end, per chain: S = the sample covariance of the window's rows (n - 1 divisor), Sigma = n / (n + 5) S +
+    1e-3 * 5 / (n + 5) I, Lam_new = chol(Sigma) (torch on the device, batched over the chains), eps = exp(xbar) *
+    (det Lam_old / det Lam_new) ** (1 / 4) -- the project's own rule, which keeps the mean physical step across the
+    change of coordinates -- and dual averaging restarts with mu = log(10 eps), m = sbar = xbar = 0.  At the end
+    eps = exp(xbar).  Launch boundaries fall on window ends; within a window the kernel adapts on its own for
+    ``steps_per_launch`` (default ``STEPS_PER_LAUNCH_HMC(n_leapfrog)``) steps per launch, and the result does not depend
+    on that number.
+
+    Returns ``HmcAdaptation``: ``step_size`` (chains,), ``metric_chol`` (chains, 4, 4) and ``last_row`` (chains, 4) to
+    go on with -- ``hmc_metric_sample(a.last_row, n, a.step_size, a.metric_chol, n_leapfrog, seed=another_seed)`` --
+    then every warm-up row with ``log_p`` and ``grad`` (row 0 is the start), ``accept_stat`` and ``step_sizes``
+    (chains, n_warmup), the list ``windows`` of ``HmcWindow`` and the counts.  The noise of warm-up step t is
+    ``hmc_sample``'s for (seed, chain, t): sample with another seed.  A START that cannot be evaluated raises
+    ValueError."""
+    import torch
+    hmc_warmup_windows(n_warmup)                    # (its check of n_warmup, before anything runs)
+    out = {}
+
+    def drive_with(eps_d, chol_d, eps, lam):
+        def drive(advance, state, samples, log_p):
+            def run_segment(start, stop, chol, da):
+                state[:, _DA_WORDS] = torch.from_numpy(np.ascontiguousarray(da)).to(state.device)
+                chol_d.copy_(torch.from_numpy(np.ascontiguousarray(chol[:, _TRIL[0], _TRIL[1]])))
+                advance(start, stop)
+                if start == 0:
+                    _check_start('hmc_warmup: the evaluation', log_p)
+                return samples[:, start + 1:stop + 1], state[:, _DA_WORDS].cpu().numpy()
+            out['eps'], out['chol'], out['windows'] = hmc_warmup_schedule(run_segment, n_warmup, eps, lam)
+        return drive
+    lam0 = np.eye(4) if metric_chol is None else metric_chol
+    run = _hmc_metric_run('hmc_warmup', log_theta_init, int(n_warmup) + 1, step_size, lam0, n_leapfrog, seed=seed,
+                          noise=noise, kick_cap=kick_cap, data=data, rtol=rtol, atol=atol, max_steps=max_steps,
+                          first_chain=first_chain, steps_per_launch=steps_per_launch, return_noise=False,
+                          device_out=device_out, delta=target_accept, drive_with=drive_with)
+    last = run.samples[:, -1].clone() if device_out else run.samples[:, -1].copy()
+    return HmcAdaptation(out['eps'], out['chol'], last, run.samples, run.log_p, run.grad, run.accept_stat,
+                         run.step_size, out['windows'], run.accepted, run.n_failed)

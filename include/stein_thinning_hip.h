@@ -535,6 +535,47 @@ int st_lv_hmc_wave(double *state, int64_t chains, int64_t first_chain, int64_t f
                    int64_t out_ld, int64_t out_row0, void *stream);
 
 /* ------------------------------------------------------------------------------------------
+ * HMC with a per-chain step size, a per-chain dense metric and step-size adaptation, one WAVE per chain
+ * (csrc/lv_mcmc.hip: lv_hmc_metric_wave_kernel).  st_lv_hmc_wave's definition with three
+ * additions, every device operation uncontracted and in this order:
+ *   (1) eps is one double per chain and the metric a per-chain factor Lam, lower triangular with M^-1 = Lam Lam^T.
+ *       The momentum stays r ~ N(0, I) (the noise and K(r) are st_lv_hmc_wave's).  In a stage
+ *         f_j(q)    = Lam_jj g_j(q) + sum_{k > j} Lam_kj g_k(q)      (the first term alone, then k ascending)
+ *         kick_j(q) = min(max(eps f_j(q), -c_j), c_j),  hk = 0.5 kick
+ *         r' = r + hk(q);  v_j = sum_{k <= j} Lam_jk r'_k (from the k = 0 term, k ascending);  q_j <- q_j + eps v_j
+ *         r  = r' + hk(q) at the new q
+ *       and the accept, failure and NaN rules are st_lv_hmc_wave's.  With Lam = I and one eps for all chains the
+ *       rows, log_p, grad and counts are st_lv_hmc_wave's bit for bit.
+ *   (2) per step, accept_stat = alpha = min(1, exp(a)), a = (lp(q^L) - lp(x)) + (K(r^0) - K(r^L)), 0 when a is NaN,
+ *       and step_size = the eps the step used.
+ *   (3) adapt = 1: eps is read from the state record and follows Stan's dual averaging after every step, with
+ *       gamma = 0.05, t0 = 10, kappa = 0.75:  m <- m + 1;  eta = 1 / (m + t0);
+ *       sbar <- (1 - eta) sbar + eta (delta - alpha);  ell = mu - (sbar sqrt(m)) / gamma;  w = pow(m, -kappa);
+ *       xbar <- (1 - w) xbar + w ell;  eps <- exp(ell).  adapt = 0: these words are neither read nor written and
+ *       eps stays eps_chain[chain].
+ * Arguments as st_lv_hmc_wave, except:
+ *   state: DEVICE, st_lv_hmc_metric_workspace_bytes(chains) = 192 chains bytes: 24 words per chain, st_lv_mala_wave's
+ *       16, then eps, m, sbar, xbar, mu (doubles; the caller sets them before an adapt = 1 launch: mu = log(10 eps),
+ *       m = sbar = xbar = 0 starts an adaptation) and three spare.  A launch ends on a step boundary and leaves the
+ *       whole state in the record, so results do not depend on how a run is split into launches;
+ *   eps_chain: DEVICE (chains);  metric_chol: DEVICE (chains, 10), the row-major packed lower triangle of Lam
+ *       (Lam_jk at j (j + 1) / 2 + k);  kick_clip: HOST (4);  adapt: 0 or 1;  delta: the target acceptance;
+ *   accept_stat, step_size: DEVICE (chains, out_ld); the step that writes row r of samples writes their row r (the
+ *       start row has none).
+ * ST_ERR_INVALID (all checked before any HIP call): the conditions of st_lv_hmc_wave but those on step_eps; eps_chain,
+ * metric_chol, accept_stat or step_size NULL or not 8-byte aligned; adapt not 0 or 1; delta not in (0, 1).
+ * ---------------------------------------------------------------------------------------- */
+int64_t st_lv_hmc_metric_workspace_bytes(int64_t chains);
+int st_lv_hmc_metric_wave(double *state, int64_t chains, int64_t first_chain, int64_t first_step, int64_t steps,
+                          int32_t init, const double *eps_chain, const double *metric_chol, const double *kick_clip,
+                          int32_t n_leapfrog, int32_t adapt, double delta, int32_t noise_mode, uint64_t seed,
+                          double *z, double *log_u, int64_t noise_ld, int64_t noise_row0, const double *t_eval,
+                          int32_t t_n, const double *y_obs, const double *span_u0_tol, const double *whiten,
+                          double c_log, double norm_logc, const double *cov_inv, int64_t max_steps, double *samples,
+                          double *log_p, double *grad, double *accept_stat, double *step_size, int64_t out_ld,
+                          int64_t out_row0, void *stream);
+
+/* ------------------------------------------------------------------------------------------
  * Integrand protocol -- replaces integrand(ind1, ind2) of the closures returned by
  * stein_thinning.thinning._make_stein_integrand / _make_stein_gf_integrand and
  * stein_thinning.kernel.vfk0_imq (restated at JAX_Stein_Thinning.ipynb cell 27, json ~354-361;
