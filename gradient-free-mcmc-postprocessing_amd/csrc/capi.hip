@@ -1057,6 +1057,59 @@ int st_lv_hmc_metric_wave(double* state, int64_t chains, int64_t first_chain, in
     return hip_check(st::launch_lv_hmc_metric_wave(a, static_cast<hipStream_t>(stream)), "lv hmc metric wave launch");
 }
 
+int64_t st_lv_nuts_workspace_bytes(int64_t chains) {
+    if (chains < 1) return -1;
+    return chains * 192;
+}
+
+int st_lv_nuts_wave(double* state, int64_t chains, int64_t first_chain, int64_t first_step, int64_t steps,
+                    int32_t init, const double* eps_chain, const double* metric_chol, const double* kick_clip,
+                    int32_t max_depth, int32_t adapt, double delta, int32_t noise_mode, uint64_t seed, double* z,
+                    double* log_u, int64_t noise_ld, int64_t noise_row0, const double* t_eval, int32_t t_n,
+                    const double* y_obs, const double* span_u0_tol, const double* whiten, double c_log,
+                    double norm_logc, const double* cov_inv, int64_t max_steps, double* samples, double* log_p,
+                    double* grad, double* accept_stat, double* step_size, double* tree_depth, double* n_leapfrog,
+                    double* divergent, int64_t out_ld, int64_t out_row0, void* stream) {
+    // the common checks (the step sizes are a device array: not theirs), then the sampler's own
+    st::LvNutsArgs a{};
+    int rc = lv_rwmh_args(a, state, chains, first_chain, first_step, steps, init, nullptr, noise_mode, seed, z,
+                          log_u, noise_ld, noise_row0, t_eval, t_n, y_obs, span_u0_tol, whiten, c_log, norm_logc,
+                          max_steps, samples, log_p, out_ld, out_row0, false);
+    if (rc) return rc;
+    if (noise_mode == 0)
+        return fail(ST_ERR_INVALID, "noise_mode must be 1 or 2: the tree's draws have no supplied-noise form");
+    if (!grad || !kick_clip || !cov_inv) return fail(ST_ERR_INVALID, "NULL pointer (grad, kick_clip, cov_inv)");
+    if (!eps_chain || !metric_chol || !accept_stat || !step_size || !tree_depth || !n_leapfrog || !divergent)
+        return fail(ST_ERR_INVALID, "NULL pointer (eps_chain, metric_chol, accept_stat, step_size, tree_depth, "
+                                    "n_leapfrog, divergent)");
+    if (!aligned16(grad)) return fail(ST_ERR_INVALID, "grad must be 16-byte aligned");
+    if (!aligned8(eps_chain) || !aligned8(metric_chol) || !aligned8(accept_stat) || !aligned8(step_size) ||
+        !aligned8(tree_depth) || !aligned8(n_leapfrog) || !aligned8(divergent))
+        return fail(ST_ERR_INVALID, "eps_chain, metric_chol and the per-step outputs must be 8-byte aligned");
+    for (int j = 0; j < 4; ++j)
+        if (!(kick_clip[j] > 0)) return fail(ST_ERR_INVALID, "kick clip %d must be > 0 (got %g)", j, kick_clip[j]);
+    if (max_depth < 1 || max_depth > 10)
+        return fail(ST_ERR_INVALID, "max_depth must be 1 .. 10 (got %d)", (int)max_depth);
+    if (adapt != 0 && adapt != 1) return fail(ST_ERR_INVALID, "adapt must be 0 or 1");
+    if (!(delta > 0 && delta < 1)) return fail(ST_ERR_INVALID, "delta must lie in (0, 1) (got %g)", delta);
+    for (int j = 0; j < 4; ++j) {
+        a.clip[j] = kick_clip[j];
+        a.cinv[j] = cov_inv[j];
+    }
+    a.eps_chain = eps_chain;
+    a.metric_chol = metric_chol;
+    a.max_depth = max_depth;
+    a.adapt = adapt;
+    a.delta = delta;
+    a.grad = grad;
+    a.accept_stat = accept_stat;
+    a.step_size = step_size;
+    a.tree_depth = tree_depth;
+    a.n_leapfrog = n_leapfrog;
+    a.divergent = divergent;
+    return hip_check(st::launch_lv_nuts_wave(a, static_cast<hipStream_t>(stream)), "lv nuts wave launch");
+}
+
 int st_greedy_finalize(const double* cands_in, int32_t nranks, int32_t d, uint32_t* idx_out,
                        int64_t t, void* stream) {
     if (!cands_in || !idx_out) return fail(ST_ERR_INVALID, "NULL pointer");

@@ -59,11 +59,11 @@ __device__ __forceinline__ double lv_logdens_one(const LvProblem& p, const doubl
     return ll + lv_log_prior(lth, p.norm_logc);
 }
 
-// Philox4x64-10 (Random123; numpy/random/src/philox): one block for counter (c0, 0, 0, 0), key (k0, k1)
-__device__ inline void philox4x64_10(uint64_t c0, uint64_t k0, uint64_t k1, uint64_t out[4]) {
+// Philox4x64-10 (Random123; numpy/random/src/philox): one block for counter (c0, c1, 0, 0), key (k0, k1)
+__device__ inline void philox4x64_10(uint64_t c0, uint64_t c1, uint64_t k0, uint64_t k1, uint64_t out[4]) {
     constexpr uint64_t M0 = 0xD2E7470EE14C6C93ull, M1 = 0xCA5A826395121157ull;
     constexpr uint64_t W0 = 0x9E3779B97F4A7C15ull, W1 = 0xBB67AE8584CAA73Bull;
-    uint64_t c[4] = {c0, 0, 0, 0};
+    uint64_t c[4] = {c0, c1, 0, 0};
 #pragma unroll
     for (int r = 0; r < 10; ++r) {
         if (r) { k0 += W0; k1 += W1; }
@@ -79,8 +79,8 @@ __device__ inline void philox4x64_10(uint64_t c0, uint64_t k0, uint64_t k1, uint
 // the noise of step t of chain `chain` (file header)
 __device__ inline void device_noise(uint64_t seed, uint64_t chain, uint64_t t, double z[4], double& log_u) {
     uint64_t r[4], q[4];
-    philox4x64_10(2 * t - 1, seed, chain, r);
-    philox4x64_10(2 * t, seed, chain, q);
+    philox4x64_10(2 * t - 1, 0, seed, chain, r);
+    philox4x64_10(2 * t, 0, seed, chain, q);
     constexpr double k2m53 = 0x1.0p-53, kTwoPi = 6.283185307179586;
     double u[4];
 #pragma unroll
@@ -826,6 +826,322 @@ __global__ __launch_bounds__(kWaveLanes * kWaveChainsPerBlock) void lv_hmc_metri
     }
 }
 
+// ---- No-U-turn sampler (NUTS), one wave per chain ----
+// lv_hmc_metric_wave_kernel's chain -- its stage, eps, Lam, cap, state record and dual averaging -- with the trajectory
+// length chosen per step by a binary tree (Hoffman & Gelman's NUTS in Betancourt's multinomial form, built iteratively
+// with checkpoints; the project's own definition, DESIGN.md section 22 is the contract).  A stage in direction v = +-1
+// is the metric kernel's stage with eps replaced by v eps.  Noise is the device's Philox only: step t takes its
+// momentum z from device_noise(seed, chain, t); stage l = 1, 2, ... of the step draws the block with counter
+// (t, l, 0, 0) = r0 .. r3: log u_l = log((r0 >> 11) 2^-53); at the first stage of a doubling v = +1 when r1 >> 63 is 0
+// and log u_T = log((r2 >> 11) 2^-53).
+// One step from the row (x, lp, g): K0 = K(z); both ends (x, z, g); rho = z; W = 0; the proposal is the row.  Doubling
+// j = 0, 1, ... builds 2^j leaves from the end on side v; leaf n = (q, r) has a_n = (lp(q) - lp) + (K0 - K(r)):
+//   sum_alpha += min(1, exp(a_n))  (0 for a NaN);  a NaN a_n or a_n < -1000: divergent, the sub-tree is dropped, stop
+//   W' = a_0, then W' <- lse(W', a_n), lse(p, s) = max(p, s) + log1p(exp(-|p - s|))
+//   the sub-tree's proposal is leaf 0; leaf n > 0 replaces it exactly when log u_l < a_n - W' (W' updated; strict)
+//   rho' = r_0, then rho' <- rho' + r_n
+//   even n: the checkpoint (r_n, rho') goes to slot popcount(n >> 1)
+//   odd n: for k = 1 .. (trailing one bits of n), the block of 2^k leaves that ends at n, first leaf m = n with its low
+//          k bits cleared and checkpoint (r_a, rho'_a) in slot popcount(m >> 1): rho_b = (rho' - rho'_a) + r_a; the block
+//          turns when NOT (dot(rho_b, r_a) > 0 AND dot(rho_b, r_n) > 0), dot from its j = 0 term; a turn drops the
+//          sub-tree and stops
+// A complete sub-tree's proposal replaces the tree's exactly when log u_T < W' - W; then W <- lse(W, W'), rho <- rho + rho',
+// the end on side v becomes the last leaf, and the trajectory stops when the whole tree turns (rho, the two ends'
+// momenta) or after max_depth doublings.  The new row is the proposal.
+// Only q, g(q), r, eps and integer flags live across the integration; the tree (ends, proposals, rho, rho', checkpoints,
+// scalars: 132 doubles) lives in a per-wave slab of LDS.  All of it is wave-uniform: EVERY lane stores the same bits to
+// the same address and reads them back after a compiler barrier, so no ordering between lanes is relied on.  There is
+// no block barrier: the four waves of a block are independent chains with different trip counts.  Branches on tree
+// values go through readfirstlane (nuts_uniform); the butterflies stay in the loop's common path.
+constexpr int kNutsMaxDepth = 10;
+constexpr int kNutsEnd = 0;               // [side][q 4, r 4, g 4], side 0: the backward end, 1: the forward end
+constexpr int kNutsProp = 24;             // the tree's proposal: x 4, g 4, lp
+constexpr int kNutsSub = 34;              // the sub-tree's proposal, likewise
+constexpr int kNutsRho = 44, kNutsRhoSub = 48;
+constexpr int kNutsW = 52, kNutsWSub = 53, kNutsSumAlpha = 54, kNutsK0 = 55, kNutsLp0 = 56, kNutsLogU = 57,
+              kNutsLogUT = 58;
+constexpr int kNutsCk = 60;               // [slot][r 4, rho' 4], kNutsMaxDepth - 1 slots
+constexpr int kNutsSlabWords = kNutsCk + 8 * (kNutsMaxDepth - 1);
+
+__device__ __forceinline__ bool nuts_uniform(bool b) { return __builtin_amdgcn_readfirstlane((int)b) != 0; }
+
+__device__ __forceinline__ double nuts_lse(double p, double s) {
+    return (p > s ? p : s) + log1p(exp(-fabs(p - s)));
+}
+
+// NOT (dot(rho, ra) > 0 AND dot(rho, rb) > 0)
+__device__ __forceinline__ bool nuts_turns(const double rho[4], const double* ra, const double* rb) {
+    double da = rho[0] * ra[0], db = rho[0] * rb[0];
+#pragma unroll
+    for (int j = 1; j < 4; ++j) { da += rho[j] * ra[j]; db += rho[j] * rb[j]; }
+    return !(da > 0.0 && db > 0.0);
+}
+
+template <bool RECORD>
+__global__ __launch_bounds__(kWaveLanes * kWaveChainsPerBlock) void lv_nuts_wave_kernel(LvNutsArgs a) {
+    __shared__ double slabs[kWaveChainsPerBlock][kNutsSlabWords];
+    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x / kWaveLanes));
+    const int lane = (int)(threadIdx.x % kWaveLanes);
+    const int64_t i = (int64_t)blockIdx.x * kWaveChainsPerBlock + wave;
+    if (i >= a.chains) return;            // the whole wave (partial last block)
+    double* sl = slabs[wave];
+    double* st = a.state + kHmcMetricStateWords * i;
+    int64_t* sti = reinterpret_cast<int64_t*>(st);
+    // the trajectory: its current point q with g(q) and its momentum r
+    double q[4], gq[4], r[4] = {0.0, 0.0, 0.0, 0.0};
+    {
+        const double2* s2 = reinterpret_cast<const double2*>(st);
+        const double2 s0 = s2[0], s1 = s2[1], g0 = s2[4], g1 = s2[5];
+        q[0] = s0.x; q[1] = s0.y; q[2] = s1.x; q[3] = s1.y;
+        gq[0] = g0.x; gq[1] = g0.y; gq[2] = g1.x; gq[3] = g1.y;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) { sl[kNutsProp + j] = q[j]; sl[kNutsProp + 4 + j] = gq[j]; }
+        sl[kNutsProp + 8] = st[4];
+    }
+    int64_t accepted = sti[5], failed = sti[6];
+    double eps = a.adapt ? st[16] : a.eps_chain[i];
+    const double* lam = a.metric_chol + 10 * i;
+    const int64_t row0 = i * a.out_ld + a.out_row0;
+    double* rows = a.samples + row0 * 4;
+    double* grads = a.grad + row0 * 4;
+    double* lps = a.log_p + row0;
+    double* zs = nullptr;
+    if (RECORD) zs = a.z + (i * a.noise_ld + a.noise_row0) * 4;
+    const uint64_t chain = (uint64_t)(a.first_chain + i);
+    constexpr double k2m53 = 0x1.0p-53;
+    int l = 0;                            // stages of step k done
+    int n = 0;                            // leaves of the current sub-tree done
+    int depth = 0;                        // doublings started
+    int back = 0;                         // the current sub-tree's direction: 1 is v = -1
+    int replaced = 0;                     // the tree's proposal has been replaced in this step
+    // k = -1: the start row itself (a.init), evaluated by the same code as every stage
+#pragma unroll 1
+    for (int64_t k = a.init ? -1 : 0; k < a.steps;) {
+        const bool start = k < 0;
+        if (!start) {
+            const uint64_t t = (uint64_t)(a.first_step + k);
+            if (l == 0) {                 // the step begins: (q, gq) is the row
+                double unused;
+                device_noise(a.seed, chain, t, r, unused);
+                if constexpr (RECORD) {
+                    if (lane == 0) {
+                        reinterpret_cast<double2*>(zs + 4 * k)[0] = make_double2(r[0], r[1]);
+                        reinterpret_cast<double2*>(zs + 4 * k)[1] = make_double2(r[2], r[3]);
+                    }
+                }
+                double s = 0.0;
+#pragma unroll
+                for (int j = 0; j < 4; ++j) s += r[j] * r[j];
+                sl[kNutsK0] = 0.5 * s;
+                sl[kNutsLp0] = sl[kNutsProp + 8];
+                sl[kNutsW] = 0.0;
+                sl[kNutsSumAlpha] = 0.0;
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    sl[kNutsRho + j] = r[j];
+#pragma unroll
+                    for (int side = 0; side < 2; ++side) {
+                        sl[kNutsEnd + 12 * side + j] = q[j];
+                        sl[kNutsEnd + 12 * side + 4 + j] = r[j];
+                        sl[kNutsEnd + 12 * side + 8 + j] = gq[j];
+                    }
+                }
+                n = 0;
+                depth = 0;
+                replaced = 0;
+            }
+            uint64_t u[4];
+            philox4x64_10(t, (uint64_t)(l + 1), a.seed, chain, u);
+            sl[kNutsLogU] = log((double)(u[0] >> 11) * k2m53);
+            if (n == 0) {                 // a doubling begins: its direction, its end
+                back = (int)(u[1] >> 63);
+                sl[kNutsLogUT] = log((double)(u[2] >> 11) * k2m53);
+                const double* e = sl + kNutsEnd + (back ? 0 : 12);
+#pragma unroll
+                for (int j = 0; j < 4; ++j) { q[j] = e[j]; r[j] = e[4 + j]; gq[j] = e[8 + j]; }
+                ++depth;
+            }
+        }
+        const double ve = back ? -eps : eps;
+        double rp[4], p[4], th[4];
+        bool ok = true;
+        {
+            double hk[4];
+            metric_half_kick(lam, gq, ve, a.clip, hk);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) rp[j] = r[j] + hk[j];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                double v = lam[j * (j + 1) / 2] * rp[0];
+#pragma unroll
+                for (int kk = 1; kk <= j; ++kk) v += lam[j * (j + 1) / 2 + kk] * rp[kk];
+                p[j] = start ? q[j] : q[j] + ve * v;
+                th[j] = exp(p[j]);
+                ok = ok && isfinite(th[j]) && th[j] != 0.0;
+            }
+        }
+        // compiler barriers (no instruction): nothing of the slab is held in registers across the integration
+        asm volatile("" ::: "memory");
+        double ll = 0.0, acc[4] = {0.0, 0.0, 0.0, 0.0};     // this lane's terms, in increasing k
+        int status = 0;
+        if (ok) {
+            int kq = lane;
+            double tq = lane < a.p.t_n ? a.p.t_eval[lane] : 0.0;
+            status = lv_integrate<10>(th, a.p, [&](double t_old, double t_new, double inv_hd, const double* y,
+                                                   const double (*Q)[rk45::kDenseOrder], bool last) {
+                lv_observe_strided<10>(a.p, kq, tq, kWaveLanes, t_old, t_new, inv_hd, y, Q, last,
+                                       [&](int kk, const double* u) {
+                                           ll += lv_loglik_term(a.p, kk, u);
+                                           lv_grad_term(a.p, a.cinv, kk, u, acc);
+                                       });
+                return 0;
+            });
+        }
+        asm volatile("" ::: "memory");
+#pragma unroll
+        for (int off = kWaveLanes / 2; off >= 1; off >>= 1) {
+            ll += __shfl_xor(ll, off);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) acc[j] += __shfl_xor(acc[j], off);
+        }
+        double lp_new = NAN, g_new[4] = {NAN, NAN, NAN, NAN};   // theta out of range, or the integration failed
+        if (ok && status == 0) {
+            lp_new = wave_first(ll) + lv_log_prior(p, a.p.norm_logc);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) g_new[j] = th[j] * wave_first(acc[j]) - p[j];
+        }
+        if (start) {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) { sl[kNutsProp + j] = q[j]; sl[kNutsProp + 4 + j] = g_new[j]; }
+            sl[kNutsProp + 8] = lp_new;
+        } else {
+            {
+                double hk[4];
+                metric_half_kick(lam, g_new, ve, a.clip, hk);
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    r[j] = rp[j] + hk[j];
+                    q[j] = p[j];
+                    gq[j] = g_new[j];
+                }
+            }
+            ++l;
+            double s = 0.0;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) s += r[j] * r[j];
+            const double da = wave_first((lp_new - sl[kNutsLp0]) + (sl[kNutsK0] - 0.5 * s));
+            const double ea = exp(da);
+            sl[kNutsSumAlpha] = sl[kNutsSumAlpha] + (da == da ? (ea < 1.0 ? ea : 1.0) : 0.0);
+            const bool divergent = nuts_uniform(!(da == da) || da < -1000.0);
+            bool stop = divergent;
+            if (!stop) {
+                double wp = da, rs[4];
+                bool take = true;
+                if (n == 0) {
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) rs[j] = r[j];
+                } else {
+                    wp = nuts_lse(sl[kNutsWSub], da);
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) rs[j] = sl[kNutsRhoSub + j] + r[j];
+                    take = nuts_uniform(sl[kNutsLogU] < da - wp);
+                }
+                sl[kNutsWSub] = wp;
+#pragma unroll
+                for (int j = 0; j < 4; ++j) sl[kNutsRhoSub + j] = rs[j];
+                if (take) {
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) { sl[kNutsSub + j] = q[j]; sl[kNutsSub + 4 + j] = gq[j]; }
+                    sl[kNutsSub + 8] = lp_new;
+                }
+                if ((n & 1) == 0) {
+                    double* ck = sl + kNutsCk + 8 * __builtin_popcount((unsigned)(n >> 1));
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) { ck[j] = r[j]; ck[4 + j] = rs[j]; }
+                } else {
+#pragma unroll 1
+                    for (int kk = 1; ((n >> (kk - 1)) & 1) && !stop; ++kk) {
+                        const int m = n & ~((1 << kk) - 1);
+                        const double* ck = sl + kNutsCk + 8 * __builtin_popcount((unsigned)(m >> 1));
+                        double rb[4];
+#pragma unroll
+                        for (int j = 0; j < 4; ++j) rb[j] = (rs[j] - ck[4 + j]) + ck[j];
+                        stop = nuts_uniform(nuts_turns(rb, ck, r));
+                    }
+                }
+            }
+            if (!stop) {
+                if (++n < (1 << (depth - 1))) continue;      // the sub-tree's next leaf
+                // the sub-tree is complete: merge it
+                const double w = sl[kNutsW], wp = sl[kNutsWSub];
+                if (nuts_uniform(sl[kNutsLogUT] < wp - w)) {
+#pragma unroll
+                    for (int j = 0; j < 9; ++j) sl[kNutsProp + j] = sl[kNutsSub + j];
+                    replaced = 1;
+                }
+                sl[kNutsW] = nuts_lse(w, wp);
+                double rho[4];
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    rho[j] = sl[kNutsRho + j] + sl[kNutsRhoSub + j];
+                    sl[kNutsRho + j] = rho[j];
+                }
+                double* e = sl + kNutsEnd + (back ? 0 : 12);
+#pragma unroll
+                for (int j = 0; j < 4; ++j) { e[j] = q[j]; e[4 + j] = r[j]; e[8 + j] = gq[j]; }
+                n = 0;
+                stop = nuts_uniform(nuts_turns(rho, sl + kNutsEnd + 4, sl + kNutsEnd + 12 + 4)) || depth >= a.max_depth;
+                if (!stop) continue;                         // the next doubling
+            }
+            // the step's end
+            const double alpha = sl[kNutsSumAlpha] / (double)l;
+            accepted += replaced;
+            failed += divergent ? 1 : 0;
+            if (lane == 0) {
+                a.accept_stat[row0 + k] = alpha;
+                a.step_size[row0 + k] = eps;
+                a.tree_depth[row0 + k] = (double)depth;
+                a.n_leapfrog[row0 + k] = (double)l;
+                a.divergent[row0 + k] = divergent ? 1.0 : 0.0;
+            }
+            if (a.adapt) {                // lv_hmc_metric_wave_kernel's recurrence
+                const double m = st[17] + 1.0, eta = 1.0 / (m + kDaT0);
+                const double sbar = (1.0 - eta) * st[18] + eta * (a.delta - alpha);
+                const double ell = st[20] - (sbar * sqrt(m)) / kDaGamma;
+                const double w = pow(m, -kDaKappa);
+                const double xbar = (1.0 - w) * st[19] + w * ell;
+                eps = exp(ell);
+                st[16] = eps;             // every lane: the same bits
+                st[17] = m;
+                st[18] = sbar;
+                st[19] = xbar;
+            }
+        }
+        // the row: the proposal
+#pragma unroll
+        for (int j = 0; j < 4; ++j) { q[j] = sl[kNutsProp + j]; gq[j] = sl[kNutsProp + 4 + j]; }
+        if (lane == 0) {
+            reinterpret_cast<double2*>(rows + 4 * k)[0] = make_double2(q[0], q[1]);
+            reinterpret_cast<double2*>(rows + 4 * k)[1] = make_double2(q[2], q[3]);
+            reinterpret_cast<double2*>(grads + 4 * k)[0] = make_double2(gq[0], gq[1]);
+            reinterpret_cast<double2*>(grads + 4 * k)[1] = make_double2(gq[2], gq[3]);
+            lps[k] = sl[kNutsProp + 8];
+        }
+        l = 0;
+        ++k;
+    }
+    if (lane == 0) {
+        double2* s2 = reinterpret_cast<double2*>(st);
+        s2[0] = make_double2(q[0], q[1]);
+        s2[1] = make_double2(q[2], q[3]);
+        s2[4] = make_double2(gq[0], gq[1]);
+        s2[5] = make_double2(gq[2], gq[3]);
+        st[4] = sl[kNutsProp + 8];
+        sti[5] = accepted;
+        sti[6] = failed;
+    }
+}
+
 // kernel[noise_mode] (supplied, Philox, Philox + record) over a.chains chains, chains_per_block to a block
 template <class Args>
 hipError_t launch_noise_mode(void (*const (&kernel)[3])(Args), const Args& a, int chains_per_block,
@@ -853,6 +1169,15 @@ hipError_t launch_lv_hmc_metric_wave(const LvHmcMetricArgs& a, hipStream_t s) {
                                                lv_hmc_metric_wave_kernel<true, false>,
                                                lv_hmc_metric_wave_kernel<true, true>}, a, kWaveChainsPerBlock,
                                               kWaveThreads, s);
+}
+
+hipError_t launch_lv_nuts_wave(const LvNutsArgs& a, hipStream_t s) {
+    const unsigned blocks = (unsigned)((a.chains + kWaveChainsPerBlock - 1) / kWaveChainsPerBlock);
+    if (a.noise_mode == 2)
+        lv_nuts_wave_kernel<true><<<blocks, kWaveThreads, 0, s>>>(a);
+    else
+        lv_nuts_wave_kernel<false><<<blocks, kWaveThreads, 0, s>>>(a);
+    return hipGetLastError();
 }
 
 hipError_t launch_lv_rwmh_wave(const LvMcmcArgs& a, hipStream_t s) {

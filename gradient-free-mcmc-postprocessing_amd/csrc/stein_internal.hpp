@@ -303,6 +303,40 @@ struct LvHmcMetricArgs {
 };
 hipError_t launch_lv_hmc_metric_wave(const LvHmcMetricArgs& a, hipStream_t s);
 
+// No-U-turn sampler on lv_hmc_metric_wave_kernel's chain, one wave per chain (csrc/lv_mcmc.hip: lv_nuts_wave_kernel);
+// the fields it shares with LvHmcMetricArgs mean the same.  noise_mode is 1 or 2: there is no supplied-noise form
+struct LvNutsArgs {
+    double* state;            // (chains, 24) words, LvHmcMetricArgs' record
+    int64_t chains;
+    int64_t first_chain;
+    int64_t first_step;
+    int64_t steps;
+    int init;
+    const double* eps_chain;
+    const double* metric_chol;
+    double clip[4];
+    int max_depth;            // doublings per step at most, 1 .. 10
+    int adapt;
+    double delta;
+    int noise_mode;
+    uint64_t seed;
+    double* z;                // (chains, noise_ld, 4): the momenta drawn (noise_mode 2)
+    double* log_u;            // neither read nor written
+    int64_t noise_ld, noise_row0;
+    LvProblem p;
+    double cinv[4];
+    double* samples;          // (chains, out_ld, 4)
+    double* log_p;            // (chains, out_ld)
+    double* grad;             // (chains, out_ld, 4)
+    double* accept_stat;      // (chains, out_ld): the mean of min(1, exp(a)) over the step's stages
+    double* step_size;        // (chains, out_ld): the eps that step used
+    double* tree_depth;       // (chains, out_ld): doublings started, as a double
+    double* n_leapfrog;       // (chains, out_ld): stages done, as a double
+    double* divergent;        // (chains, out_ld): 0.0 or 1.0
+    int64_t out_ld, out_row0;
+};
+hipError_t launch_lv_nuts_wave(const LvNutsArgs& a, hipStream_t s);
+
 hipError_t launch_greedy_rank_exchange(const double* recs, int K, int64_t stride, int d,
                                        const MailboxPeers& peers, int rank, int nranks, int64_t t,
                                        double* recv, unsigned* status, hipStream_t s);

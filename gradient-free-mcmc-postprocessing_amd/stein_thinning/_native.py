@@ -125,6 +125,13 @@ SIGNATURES = {
                                              _i32, ctypes.c_uint64, _c_dp, _c_dp, _i64, _i64, _c_dp, _i32, _c_dp, _c_dp,
                                              _c_dp, _f64, _f64, _c_dp, _i64, _c_dp, _c_dp, _c_dp, _c_dp, _c_dp, _i64,
                                              _i64, _c_dp]),
+    'st_lv_nuts_workspace_bytes': (_i64, [_i64]),
+    # st_lv_hmc_metric_wave's arguments with max_depth in n_leapfrog's place and the device arrays tree_depth,
+    # n_leapfrog, divergent after step_size
+    'st_lv_nuts_wave': (ctypes.c_int, [_c_dp, _i64, _i64, _i64, _i64, _i32, _c_dp, _c_dp, _c_dp, _i32, _i32, _f64,
+                                       _i32, ctypes.c_uint64, _c_dp, _c_dp, _i64, _i64, _c_dp, _i32, _c_dp, _c_dp,
+                                       _c_dp, _f64, _f64, _c_dp, _i64, _c_dp, _c_dp, _c_dp, _c_dp, _c_dp, _c_dp, _c_dp,
+                                       _c_dp, _i64, _i64, _c_dp]),
     'st_kde_workspace_bytes': (_i64, [_i64, _i32]),
     'st_kde_logpdf_grad': (ctypes.c_int, [_c_dp, _i64, _i64, _c_dp, _f64, _c_dp, _i64, _i64, _i32, _f64, _c_dp,
                                           _c_dp, _c_dp, _c_dp, _i64, _c_dp]),

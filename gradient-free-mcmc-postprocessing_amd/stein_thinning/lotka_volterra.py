@@ -504,6 +504,21 @@ def STEPS_PER_LAUNCH_HMC(n_leapfrog: int) -> int:
     return max(1, 64 // int(n_leapfrog))
 
 
+NUTS_MAX_DEPTH = 10                  # the kernel's checkpoint slots: a step is at most 2**10 - 1 = 1023 stages
+
+
+def STEPS_PER_LAUNCH_NUTS(max_depth: int) -> int:
+    """Steps per launch of ``nuts_sample`` for trees of at most ``max_depth`` doublings."""
+    # STEPS_PER_LAUNCH_HMC's launch of 64 stages, taken at the worst case of 2**max_depth - 1 stages per step.  From
+    # depth 6 on it is one step per launch, and one step at depth 10 can be 1023 stages.  MEASURED on MI355X
+    # (tools/lv_nuts_bench.py, profiles/lv_nuts_bench.json): a stage takes 0.189-0.195 ms at 5 to 1024 chains and
+    # 0.77 ms at 4096; the worst case, a launch in which a chain runs all 1023 stages, 0.194 s at 64 chains, 0.195 s
+    # at 1024 and 0.769 s at 4096 -- above the quarter of a second a launch is meant to stay below: with thousands of
+    # chains max_depth 8 (255 stages) keeps to it.  The reference-shaped run's longest step was 103 stages (0.02 s).
+    # Other splits were not timed.  Results do not depend on it.
+    return max(1, 64 // (2 ** int(max_depth) - 1))
+
+
 @dataclass
 class HmcSample:
     """Result of ``hmc_sample`` (NumPy arrays, or ROCm tensors with ``device_out=True``)."""
@@ -600,6 +615,26 @@ class HmcMetricSample:
     step_size: object = None          # (chains, n_samples - 1): the eps that step used
     adapt_state: object = None        # (chains, 5) eps, m, sbar, xbar, mu after the last step (target_accept given)
     adapt_trace: object = None        # (launches, chains, 5): the same after every launch (return_adapt_trace)
+
+
+@dataclass
+class NutsSample:
+    """Result of ``nuts_sample``: ``HmcMetricSample``'s fields (``log_u`` stays None: the sampler has no accept
+    draw), then the tree's per-step outputs."""
+    samples: object
+    log_p: object
+    grad: object
+    accepted: object                  # (chains,) int64: steps whose row was replaced at least once
+    n_failed: object                  # (chains,) int64: divergent steps
+    z: object = None
+    log_u: object = None
+    accept_stat: object = None        # (chains, n_samples - 1): the mean of min(1, exp(a)) over the step's stages
+    step_size: object = None
+    adapt_state: object = None
+    adapt_trace: object = None
+    tree_depth: object = None         # (chains, n_samples - 1) int32: doublings started
+    n_leapfrog: object = None         # (chains, n_samples - 1) int32: stages done
+    divergent: object = None          # (chains, n_samples - 1) bool
 
 
 @dataclass
@@ -749,9 +784,12 @@ _TRIL = np.tril_indices(4)            # row-major order of the lower triangle: t
 
 
 def _hmc_metric_run(who, log_theta_init, n_samples, step_size, metric_chol, n_leapfrog, *, seed, noise, kick_cap, data,
-                    rtol, atol, max_steps, first_chain, steps_per_launch, return_noise, device_out, delta, drive_with):
-    """The checks and the launch closure ``hmc_metric_sample`` and ``hmc_warmup`` share.  ``drive_with(eps_d, chol_d)``
-    returns ``_run_chains``' drive (or None) given the device arrays the launches read."""
+                    rtol, atol, max_steps, first_chain, steps_per_launch, return_noise, device_out, delta, drive_with,
+                    max_depth=None, nuts=False):
+    """The checks and the launch closure ``hmc_metric_sample``, ``hmc_warmup``, ``nuts_sample`` and ``nuts_warmup``
+    share.  ``drive_with(eps_d, chol_d, eps, lam)`` returns ``_run_chains``' drive (or None) given the device arrays
+    the launches read.  ``nuts`` runs the NUTS kernel with ``max_depth`` (``n_leapfrog`` is not used) and returns
+    ``NutsSample``."""
     import torch
     x0, n_samples, _ = _chain_start(log_theta_init, n_samples, 1.0)
     chains = x0.shape[0]
@@ -763,9 +801,16 @@ def _hmc_metric_run(who, log_theta_init, n_samples, step_size, metric_chol, n_le
     if not np.all(np.isfinite(eps)) or np.any(eps <= 0):
         raise ValueError(f'step_size must be finite and > 0, got {step_size!r}')
     lam = _metric_chol(metric_chol, chains)
-    if isinstance(n_leapfrog, bool) or not isinstance(n_leapfrog, (int, np.integer)) or not 1 <= n_leapfrog < 2 ** 31:
-        raise ValueError(f'n_leapfrog must be an integer >= 1, got {n_leapfrog!r}')
-    n_leapfrog = int(n_leapfrog)
+    if nuts:
+        if isinstance(max_depth, bool) or not isinstance(max_depth, (int, np.integer)) or \
+                not 1 <= max_depth <= NUTS_MAX_DEPTH:
+            raise ValueError(f'max_depth must be an integer from 1 to {NUTS_MAX_DEPTH}, got {max_depth!r}')
+        length, default_spl = int(max_depth), STEPS_PER_LAUNCH_NUTS(int(max_depth))
+    else:
+        if isinstance(n_leapfrog, bool) or not isinstance(n_leapfrog, (int, np.integer)) or \
+                not 1 <= n_leapfrog < 2 ** 31:
+            raise ValueError(f'n_leapfrog must be an integer >= 1, got {n_leapfrog!r}')
+        length, default_spl = int(n_leapfrog), STEPS_PER_LAUNCH_HMC(int(n_leapfrog))
     try:
         cap = float(kick_cap)
     except (TypeError, ValueError):
@@ -777,24 +822,96 @@ def _hmc_metric_run(who, log_theta_init, n_samples, step_size, metric_chol, n_le
         raise ValueError(f'target_accept must lie in (0, 1), got {delta!r}')
     clip = np.full(4, cap)
     seed, noise, spl = _chain_noise(chains, n_samples - 1, seed, noise, first_chain, steps_per_launch,
-                                    STEPS_PER_LAUNCH_HMC(n_leapfrog), max_steps)
+                                    default_spl, max_steps)
     problem = _chain_problem(data, rtol, atol)
     cinv = np.ascontiguousarray(np.linalg.inv(np.asarray(problem[0].cov, dtype=np.float64)))
     dev = nat.require_device()
     eps_d = torch.from_numpy(np.ascontiguousarray(eps)).to(dev)
     chol_d = torch.from_numpy(np.ascontiguousarray(lam[:, _TRIL[0], _TRIL[1]])).to(dev)
+    name = 'st_lv_nuts_wave' if nuts else 'st_lv_hmc_metric_wave'
 
     def launch(L, head, mid, rows, extra, tail):
-        nat.check(L.st_lv_hmc_metric_wave(*head, nat.ptr(eps_d), nat.ptr(chol_d), clip.ctypes.data, n_leapfrog,
-                                          1 if adapt else 0, float(delta) if adapt else 0.5, *mid, cinv.ctypes.data,
-                                          *rows, *extra, *tail), 'st_lv_hmc_metric_wave')
+        nat.check(getattr(L, name)(*head, nat.ptr(eps_d), nat.ptr(chol_d), clip.ctypes.data, length,
+                                   1 if adapt else 0, float(delta) if adapt else 0.5, *mid, cinv.ctypes.data,
+                                   *rows, *extra, *tail), name)
     res = _run_chains(
         failed_start=f'{who}: the evaluation', x0=x0, n_samples=n_samples, seed=seed, noise=noise,
         first_chain=first_chain, spl=spl, max_steps=max_steps, problem=problem, return_noise=return_noise,
-        device_out=device_out, state_words=24, n_extra=1, launch=launch, n_extra_rows=2,
+        device_out=device_out, state_words=24, n_extra=1, launch=launch, n_extra_rows=5 if nuts else 2,
         drive=drive_with(eps_d, chol_d, eps, lam))
-    samples, log_p, grad, alpha, eps_used, accepted, n_failed, z, log_u = res
-    return HmcMetricSample(samples, log_p, grad, accepted, n_failed, z, log_u, alpha[:, 1:], eps_used[:, 1:])
+    if not nuts:
+        samples, log_p, grad, alpha, eps_used, accepted, n_failed, z, log_u = res
+        return HmcMetricSample(samples, log_p, grad, accepted, n_failed, z, log_u, alpha[:, 1:], eps_used[:, 1:])
+    samples, log_p, grad, alpha, eps_used, depth, stages, div, accepted, n_failed, z, _ = res
+    if device_out:
+        depth, stages, div = depth[:, 1:].to(torch.int32), stages[:, 1:].to(torch.int32), div[:, 1:] != 0
+    else:
+        depth, stages, div = depth[:, 1:].astype(np.int32), stages[:, 1:].astype(np.int32), div[:, 1:] != 0
+    # the kernel neither reads nor writes log_u
+    return NutsSample(samples, log_p, grad, accepted, n_failed, z, None, alpha[:, 1:], eps_used[:, 1:],
+                      tree_depth=depth, n_leapfrog=stages, divergent=div)
+
+
+def _adapt_drive_with(out, n_samples, target_accept, adapt_state, return_adapt_trace):
+    """``_hmc_metric_run``'s ``drive_with`` for a sampling run: with ``target_accept`` the dual-averaging state is put
+    into the state record before the first launch and read back into ``out`` ('state', 'trace') after the last."""
+    import torch
+
+    def drive_with(eps_d, chol_d, eps, lam):
+        if target_accept is None:
+            if adapt_state is not None or return_adapt_trace:
+                raise ValueError('adapt_state and return_adapt_trace need target_accept')
+            return None
+        da0 = hmc_adapt_restart(eps) if adapt_state is None else np.array(adapt_state, dtype=np.float64)
+        if da0.shape != (eps.size, 5) or not np.all(np.isfinite(da0)) or np.any(da0[:, 0] <= 0) or np.any(da0[:, 1] < 0):
+            raise ValueError(f'adapt_state must be ({eps.size}, 5) finite values eps > 0, m >= 0, sbar, xbar, mu')
+
+        def drive(advance, state, samples, log_p):
+            state[:, _DA_WORDS] = torch.from_numpy(da0).to(state.device)
+            trace = []
+            advance(0, samples.shape[1] - 1,
+                    each=(lambda: trace.append(state[:, _DA_WORDS].clone())) if return_adapt_trace else None)
+            out['state'] = state[:, _DA_WORDS].clone()
+            if samples.shape[1] - 1 > int(n_samples) - 1:       # a one-row run: its spare step is dropped
+                out['state'], trace = torch.from_numpy(da0).to(state.device), trace[:0]
+            out['trace'] = (torch.stack(trace) if trace else state.new_empty((0, eps.size, 5))) \
+                if return_adapt_trace else None
+        return drive
+    return drive_with
+
+
+def _adapt_result(run, out, target_accept, device_out):
+    """``run`` with the dual-averaging state and trace that ``_adapt_drive_with`` left in ``out``."""
+    if target_accept is not None:
+        run.adapt_state = out['state'] if device_out else out['state'].cpu().numpy()
+        if out['trace'] is not None:
+            run.adapt_trace = out['trace'] if device_out else out['trace'].cpu().numpy()
+    return run
+
+
+def _warmup_drive_with(out, who, n_warmup):
+    """``_hmc_metric_run``'s ``drive_with`` for a warm-up: ``hmc_warmup_schedule`` with a ``run_segment`` that sets the
+    dual-averaging state and the metric and launches the segment's steps; eps, Lam and the windows go to ``out``."""
+    import torch
+
+    def drive_with(eps_d, chol_d, eps, lam):
+        def drive(advance, state, samples, log_p):
+            def run_segment(start, stop, chol, da):
+                state[:, _DA_WORDS] = torch.from_numpy(np.ascontiguousarray(da)).to(state.device)
+                chol_d.copy_(torch.from_numpy(np.ascontiguousarray(chol[:, _TRIL[0], _TRIL[1]])))
+                advance(start, stop)
+                if start == 0:
+                    _check_start(f'{who}: the evaluation', log_p)
+                return samples[:, start + 1:stop + 1], state[:, _DA_WORDS].cpu().numpy()
+            out['eps'], out['chol'], out['windows'] = hmc_warmup_schedule(run_segment, n_warmup, eps, lam)
+        return drive
+    return drive_with
+
+
+def _warmup_result(run, out, device_out):
+    last = run.samples[:, -1].clone() if device_out else run.samples[:, -1].copy()
+    return HmcAdaptation(out['eps'], out['chol'], last, run.samples, run.log_p, run.grad, run.accept_stat,
+                         run.step_size, out['windows'], run.accepted, run.n_failed)
 
 
 def hmc_metric_sample(log_theta_init, n_samples, step_size, metric_chol, n_leapfrog, *, seed=None, noise=None,
@@ -805,8 +922,8 @@ def hmc_metric_sample(log_theta_init, n_samples, step_size, metric_chol, n_leapf
                       device_out: bool = False) -> HmcMetricSample:
     """HMC chains on the LV log posterior with a step size per chain and a dense metric per chain, one chain per GPU
     wave (``st_lv_hmc_metric_wave``, csrc/lv_mcmc.hip): ``hmc_sample`` as Stan's adapted sampler would run it after
-    ``hmc_warmup``.  This is the project's own definition; Stan's bits are not claimed, and there is neither NUTS nor
-    a jittered trajectory length.
+    ``hmc_warmup``.  This is the project's own definition; Stan's bits are not claimed.  The trajectory length is
+    fixed (no jitter); ``nuts_sample`` chooses it per step.
 
     Definition.  ``step_size`` is eps, a scalar or (chains,) -- one per CHAIN, not per component as in ``hmc_sample``;
     ``metric_chol`` is Lam, (4, 4) or (chains, 4, 4), lower triangular with a positive diagonal (anything else raises
@@ -830,38 +947,13 @@ def hmc_metric_sample(log_theta_init, n_samples, step_size, metric_chol, n_leapf
     chain's state record, so the result does not depend on ``steps_per_launch`` (default
     ``STEPS_PER_LAUNCH_HMC(n_leapfrog)``); a chain is bit-identical to itself under any launch split, any
     ``first_chain`` offset, with or without ``return_noise``, and when re-run from its recorded noise."""
-    import torch
     out = {}
-
-    def drive_with(eps_d, chol_d, eps, lam):
-        if target_accept is None:
-            if adapt_state is not None or return_adapt_trace:
-                raise ValueError('adapt_state and return_adapt_trace need target_accept')
-            return None
-        da0 = hmc_adapt_restart(eps) if adapt_state is None else np.array(adapt_state, dtype=np.float64)
-        if da0.shape != (eps.size, 5) or not np.all(np.isfinite(da0)) or np.any(da0[:, 0] <= 0) or np.any(da0[:, 1] < 0):
-            raise ValueError(f'adapt_state must be ({eps.size}, 5) finite values eps > 0, m >= 0, sbar, xbar, mu')
-
-        def drive(advance, state, samples, log_p):
-            state[:, _DA_WORDS] = torch.from_numpy(da0).to(state.device)
-            trace = []
-            advance(0, samples.shape[1] - 1,
-                    each=(lambda: trace.append(state[:, _DA_WORDS].clone())) if return_adapt_trace else None)
-            out['state'] = state[:, _DA_WORDS].clone()
-            if samples.shape[1] - 1 > int(n_samples) - 1:       # a one-row run: its spare step is dropped
-                out['state'], trace = torch.from_numpy(da0).to(state.device), trace[:0]
-            out['trace'] = (torch.stack(trace) if trace else state.new_empty((0, eps.size, 5))) \
-                if return_adapt_trace else None
-        return drive
     run = _hmc_metric_run('hmc_metric_sample', log_theta_init, n_samples, step_size, metric_chol, n_leapfrog, seed=seed,
                           noise=noise, kick_cap=kick_cap, data=data, rtol=rtol, atol=atol, max_steps=max_steps,
                           first_chain=first_chain, steps_per_launch=steps_per_launch, return_noise=return_noise,
-                          device_out=device_out, delta=target_accept, drive_with=drive_with)
-    if target_accept is not None:
-        run.adapt_state = out['state'] if device_out else out['state'].cpu().numpy()
-        if out['trace'] is not None:
-            run.adapt_trace = out['trace'] if device_out else out['trace'].cpu().numpy()
-    return run
+                          device_out=device_out, delta=target_accept,
+                          drive_with=_adapt_drive_with(out, n_samples, target_accept, adapt_state, return_adapt_trace))
+    return _adapt_result(run, out, target_accept, device_out)
 
 
 def hmc_warmup(log_theta_init, n_warmup, step_size, n_leapfrog, *, target_accept: float = 0.8, metric_chol=None,
@@ -871,8 +963,9 @@ def hmc_warmup(log_theta_init, n_warmup, step_size, n_leapfrog, *, target_accept
     """Warm-up for ``hmc_metric_sample``: ``n_warmup`` HMC steps per chain during which the step size is tuned to the
     acceptance ``target_accept`` by dual averaging inside the kernel and a dense metric is learned from the draws in
     windows.  It follows Stan's warm-up -- Hoffman & Gelman's dual averaging, Stan's windows and its regularisation of
-    the covariance -- but these are this project's own definitions and Stan's bits are not claimed; NUTS, jittered
-    trajectory lengths and Stan's search for a first step size are out of scope.
+    the covariance -- but these are this project's own definitions and Stan's bits are not claimed; jittered
+    trajectory lengths and Stan's search for a first step size are out of scope.  ``nuts_warmup`` is the same
+    warm-up with the trajectory length chosen by the no-U-turn rule, for ``nuts_sample``.
 
     Schedule (``hmc_warmup_windows``): 75 steps that adapt eps only, slow windows of 25, 50, 100, ... steps (the last
     stretched to the end of the slow region), 50 final steps that adapt eps only; 15 % / 10 % / one window where
@@ -892,26 +985,76 @@ def hmc_warmup(log_theta_init, n_warmup, step_size, n_leapfrog, *, target_accept
     (chains, n_warmup), the list ``windows`` of ``HmcWindow`` and the counts.  The noise of warm-up step t is
     ``hmc_sample``'s for (seed, chain, t): sample with another seed.  A START that cannot be evaluated raises
     ValueError."""
-    import torch
     hmc_warmup_windows(n_warmup)                    # (its check of n_warmup, before anything runs)
     out = {}
-
-    def drive_with(eps_d, chol_d, eps, lam):
-        def drive(advance, state, samples, log_p):
-            def run_segment(start, stop, chol, da):
-                state[:, _DA_WORDS] = torch.from_numpy(np.ascontiguousarray(da)).to(state.device)
-                chol_d.copy_(torch.from_numpy(np.ascontiguousarray(chol[:, _TRIL[0], _TRIL[1]])))
-                advance(start, stop)
-                if start == 0:
-                    _check_start('hmc_warmup: the evaluation', log_p)
-                return samples[:, start + 1:stop + 1], state[:, _DA_WORDS].cpu().numpy()
-            out['eps'], out['chol'], out['windows'] = hmc_warmup_schedule(run_segment, n_warmup, eps, lam)
-        return drive
     lam0 = np.eye(4) if metric_chol is None else metric_chol
     run = _hmc_metric_run('hmc_warmup', log_theta_init, int(n_warmup) + 1, step_size, lam0, n_leapfrog, seed=seed,
                           noise=noise, kick_cap=kick_cap, data=data, rtol=rtol, atol=atol, max_steps=max_steps,
                           first_chain=first_chain, steps_per_launch=steps_per_launch, return_noise=False,
-                          device_out=device_out, delta=target_accept, drive_with=drive_with)
-    last = run.samples[:, -1].clone() if device_out else run.samples[:, -1].copy()
-    return HmcAdaptation(out['eps'], out['chol'], last, run.samples, run.log_p, run.grad, run.accept_stat,
-                         run.step_size, out['windows'], run.accepted, run.n_failed)
+                          device_out=device_out, delta=target_accept,
+                          drive_with=_warmup_drive_with(out, 'hmc_warmup', n_warmup))
+    return _warmup_result(run, out, device_out)
+
+
+def nuts_sample(log_theta_init, n_samples, step_size, metric_chol=None, *, max_depth: int = NUTS_MAX_DEPTH, seed=None,
+                kick_cap: float = math.inf, target_accept: Optional[float] = None, adapt_state=None,
+                return_adapt_trace: bool = False, data: Optional[LvData] = None, rtol: float = RTOL,
+                atol: float = ATOL, max_steps: int = MAX_STEPS, first_chain: int = 0,
+                steps_per_launch: Optional[int] = None, return_noise: bool = False,
+                device_out: bool = False) -> NutsSample:
+    """No-U-turn sampler (NUTS) chains on the LV log posterior, one chain per GPU wave (``st_lv_nuts_wave``,
+    csrc/lv_mcmc.hip): ``hmc_metric_sample`` with the trajectory length chosen per step, the counterpart of the Stan
+    stage of the reference's ``Sampling.ipynb``.  It follows Hoffman & Gelman's NUTS in Betancourt's multinomial form,
+    built iteratively with checkpoints; it is the project's own definition, Stan's bits and its
+    further cross-sub-tree U-turn checks are not claimed.
+
+    ``step_size`` (a scalar or (chains,)), ``metric_chol`` (default: the identity), ``kick_cap``, the stage, and
+    ``target_accept`` / ``adapt_state`` / ``return_adapt_trace`` are ``hmc_metric_sample``'s; a stage in direction
+    v = -1 is the stage with -eps.  One step from the row (x, lp, g) with momentum z (``hmc_sample``'s z for the same
+    seed, chain and step): for j = 0 .. max_depth - 1 a direction v is drawn and 2^j stages extend the trajectory from
+    its end on side v.  Leaf n = (q, r) has a_n = (lp(q) - lp) + (K(z) - K(r)) and weight exp(a_n); a NaN a_n (a stage
+    without a density) or a_n < -1000 makes the step *divergent*: the sub-tree is dropped and the step ends.  Inside
+    the sub-tree leaf n > 0 replaces the sub-tree's proposal when log u < a_n - W' (W' the log of the weights so
+    far); every aligned block of 2^k leaves is tested for a U-turn -- NOT (rho . r_first > 0 AND rho . r_last > 0),
+    rho the block's momentum sum -- and a turn drops the sub-tree and ends the step.  A complete sub-tree's proposal
+    replaces the tree's when log u_T < W' - W; the step ends when the whole tree turns or after ``max_depth``
+    (1 .. 10) doublings.  The next row is the proposal.  Each stage is a volume-preserving map whose inverse is the
+    stage with -eps, also under the cap, so a trajectory is an orbit and the selection with the true H keeps the
+    target.
+
+    Noise is the device's Philox only (``seed`` is required, ``noise=`` is not accepted): stage l = 1, 2, ... of step
+    t draws ``np.random.Philox(key=[seed, chain], counter=[t - 1, l, 0, 0]).random_raw(4)``.  ``return_noise`` returns
+    z; ``log_u`` stays None.
+
+    Returns ``NutsSample``: ``accept_stat`` is the mean of min(1, exp(a_n)) over the step's stages (what dual
+    averaging is fed), ``tree_depth`` the doublings started, ``n_leapfrog`` the stages done, ``divergent`` the flag;
+    ``accepted`` counts the steps whose row was replaced, ``n_failed`` the divergent steps.  ``steps_per_launch``
+    (default ``STEPS_PER_LAUNCH_NUTS(max_depth)``) splits the run into launches; a chain is bit-identical to itself
+    under any launch split, any ``first_chain`` offset and with or without ``return_noise``."""
+    out = {}
+    run = _hmc_metric_run('nuts_sample', log_theta_init, n_samples, step_size,
+                          np.eye(4) if metric_chol is None else metric_chol, None, seed=seed, noise=None,
+                          kick_cap=kick_cap, data=data, rtol=rtol, atol=atol, max_steps=max_steps,
+                          first_chain=first_chain, steps_per_launch=steps_per_launch, return_noise=return_noise,
+                          device_out=device_out, delta=target_accept, max_depth=max_depth, nuts=True,
+                          drive_with=_adapt_drive_with(out, n_samples, target_accept, adapt_state, return_adapt_trace))
+    return _adapt_result(run, out, target_accept, device_out)
+
+
+def nuts_warmup(log_theta_init, n_warmup, step_size, *, max_depth: int = NUTS_MAX_DEPTH, target_accept: float = 0.8,
+                metric_chol=None, seed=None, kick_cap: float = math.inf, data: Optional[LvData] = None,
+                rtol: float = RTOL, atol: float = ATOL, max_steps: int = MAX_STEPS, first_chain: int = 0,
+                steps_per_launch: Optional[int] = None, device_out: bool = False) -> HmcAdaptation:
+    """Warm-up for ``nuts_sample``: ``hmc_warmup``'s schedule (``hmc_warmup_schedule``: dual averaging of the step
+    size inside the kernel, the metric learned in windows) with NUTS steps of at most ``max_depth`` doublings, fed
+    with the tree's ``accept_stat``.  Returns ``HmcAdaptation``; go on with
+    ``nuts_sample(a.last_row, n, a.step_size, a.metric_chol, seed=another_seed)``."""
+    hmc_warmup_windows(n_warmup)                    # (its check of n_warmup, before anything runs)
+    out = {}
+    run = _hmc_metric_run('nuts_warmup', log_theta_init, int(n_warmup) + 1, step_size,
+                          np.eye(4) if metric_chol is None else metric_chol, None, seed=seed, noise=None,
+                          kick_cap=kick_cap, data=data, rtol=rtol, atol=atol, max_steps=max_steps,
+                          first_chain=first_chain, steps_per_launch=steps_per_launch, return_noise=False,
+                          device_out=device_out, delta=target_accept, max_depth=max_depth, nuts=True,
+                          drive_with=_warmup_drive_with(out, 'nuts_warmup', n_warmup))
+    return _warmup_result(run, out, device_out)

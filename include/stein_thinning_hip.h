@@ -576,6 +576,42 @@ int st_lv_hmc_metric_wave(double *state, int64_t chains, int64_t first_chain, in
                           int64_t out_row0, void *stream);
 
 /* ------------------------------------------------------------------------------------------
+ * No-U-turn sampler (NUTS) on st_lv_hmc_metric_wave's chain, one WAVE per chain (csrc/lv_mcmc.hip:
+ * lv_nuts_wave_kernel; DESIGN.md section 22 is the contract).  The stage, eps_chain, metric_chol, the kick cap, the
+ * 24-word state record and the dual averaging (adapt, delta) are st_lv_hmc_metric_wave's; the number of stages of a
+ * step is chosen by the tree: doubling in a random direction (a stage in direction -1 is the stage with -eps), the
+ * U-turn test on every aligned sub-tree from checkpoints, multinomial selection of the next row, and the divergence
+ * rule (a leaf whose a = (lp(q) - lp(x)) + (K(z) - K(r)) is NaN or below -1000 ends the step).  The project's own
+ * definition: Stan's bits and its further cross-sub-tree checks are not claimed.
+ * Noise is the device's Philox only, key (seed, chain): step t takes its momentum from st_lv_hmc_wave's noise of
+ * (seed, chain, t) -- the same z -- and stage l = 1, 2, ... of the step draws the block with counter (t, l, 0, 0), i.e.
+ * np.random.Philox(key=[seed, chain], counter=[t - 1, l, 0, 0]).random_raw(4) = r0 .. r3: log u_l = log((r0 >> 11) 2^-53)
+ * for the choice inside a sub-tree; at the first stage of a doubling the direction is +1 when r1 >> 63 is 0 and
+ * log u_T = log((r2 >> 11) 2^-53) decides between the tree and the new sub-tree.
+ * Arguments as st_lv_hmc_metric_wave, except:
+ *   max_depth (in n_leapfrog's place): the largest number of doublings of a step, 1 .. 10 (a step is at most
+ *       2^max_depth - 1 stages);
+ *   noise_mode: 1 (Philox) or 2 (Philox, z written to the caller's array); log_u is checked as st_lv_hmc_metric_wave
+ *       checks it and is neither read nor written;
+ *   accept_stat: the mean over the step's stages of min(1, exp(a)) (0 for a NaN a);
+ *   tree_depth, n_leapfrog, divergent: DEVICE (chains, out_ld) doubles after step_size: the doublings started, the
+ *       stages done, and 0.0 or 1.0; the step that writes row r of samples writes their row r.
+ * The state's accepted counts the steps whose row was replaced at least once, n_failed the divergent steps.
+ * state: st_lv_nuts_workspace_bytes(chains) = 192 chains bytes.
+ * ST_ERR_INVALID (all checked before any HIP call): the conditions of st_lv_hmc_metric_wave but that on n_leapfrog;
+ * noise_mode 0; max_depth outside 1 .. 10; tree_depth, n_leapfrog or divergent NULL or not 8-byte aligned.
+ * ---------------------------------------------------------------------------------------- */
+int64_t st_lv_nuts_workspace_bytes(int64_t chains);
+int st_lv_nuts_wave(double *state, int64_t chains, int64_t first_chain, int64_t first_step, int64_t steps,
+                    int32_t init, const double *eps_chain, const double *metric_chol, const double *kick_clip,
+                    int32_t max_depth, int32_t adapt, double delta, int32_t noise_mode, uint64_t seed, double *z,
+                    double *log_u, int64_t noise_ld, int64_t noise_row0, const double *t_eval, int32_t t_n,
+                    const double *y_obs, const double *span_u0_tol, const double *whiten, double c_log,
+                    double norm_logc, const double *cov_inv, int64_t max_steps, double *samples, double *log_p,
+                    double *grad, double *accept_stat, double *step_size, double *tree_depth, double *n_leapfrog,
+                    double *divergent, int64_t out_ld, int64_t out_row0, void *stream);
+
+/* ------------------------------------------------------------------------------------------
  * Integrand protocol -- replaces integrand(ind1, ind2) of the closures returned by
  * stein_thinning.thinning._make_stein_integrand / _make_stein_gf_integrand and
  * stein_thinning.kernel.vfk0_imq (restated at JAX_Stein_Thinning.ipynb cell 27, json ~354-361;
