@@ -873,6 +873,33 @@ int st_mvt_moments(const double* x, int64_t n, int32_t d, const double* loc, con
     return hip_check(st::launch_mvt_moments(a, static_cast<hipStream_t>(stream)), "mvt moments launch");
 }
 
+int64_t st_mixture_em_workspace_bytes(int64_t n, int32_t d, int32_t k) {
+    if (n < 1 || d < 1 || d > st::kMixtureEmMaxDim || k < 1 || k > st::kMixtureEmMaxComponents) return -1;
+    return st::mixture_em_ws_bytes(n, d, k);
+}
+
+int st_mixture_em_stats(const double* x, int64_t n, int32_t d, int32_t k, const double* log_coef, const double* means,
+                        const double* precision, const double* row_weights, double* out, double* log_p_out,
+                        void* workspace, int64_t workspace_bytes, void* stream) {
+    if (n < 1) return fail(ST_ERR_INVALID, "n must be >= 1 (got %lld)", (long long)n);
+    if (d < 1) return fail(ST_ERR_INVALID, "d must be >= 1 (got %d)", d);
+    if (k < 1) return fail(ST_ERR_INVALID, "k must be >= 1 (got %d)", k);
+    if (!x || !log_coef || !means || !precision || !out || !workspace) return fail(ST_ERR_INVALID, "NULL pointer");
+    if (!aligned8(x) || !aligned8(log_coef) || !aligned8(means) || !aligned8(precision) || !aligned8(row_weights) ||
+        !aligned8(out) || !aligned8(log_p_out) || !aligned8(workspace))
+        return fail(ST_ERR_INVALID, "device arrays must be 8-byte aligned");
+    if (d > st::kMixtureEmMaxDim)
+        return fail(ST_ERR_UNSUPPORTED, "d = %d exceeds the EM kernel's maximum %d", d, st::kMixtureEmMaxDim);
+    if (k > st::kMixtureEmMaxComponents)
+        return fail(ST_ERR_UNSUPPORTED, "k = %d components exceed the EM kernel's maximum %d", k,
+                    st::kMixtureEmMaxComponents);
+    if (workspace_bytes < st::mixture_em_ws_bytes(n, d, k))
+        return fail(ST_ERR_INVALID, "workspace too small (%lld < %lld)", (long long)workspace_bytes,
+                    (long long)st::mixture_em_ws_bytes(n, d, k));
+    st::MixtureEmArgs a{x, log_coef, means, precision, row_weights, n, d, k, out, log_p_out, static_cast<double*>(workspace)};
+    return hip_check(st::launch_mixture_em(a, static_cast<hipStream_t>(stream)), "mixture EM launch");
+}
+
 int st_lv_grad_log_posterior(const double* theta, int64_t n, const double* t_eval, int32_t t_n,
                              const double* y_obs, const double* span_u0_tol, const double* cov_inv,
                              int64_t max_steps, double* grad_out, int32_t* status, void* stream) {

@@ -615,3 +615,4 @@ hipError_t launch_proxy(const ProxyArgs& a, hipStream_t s) {
 
 #include "mixture.hpp"   // the Gaussian-mixture kernels: this file's tile constants and matrix-core lane maps
 #include "mvt_moments.hpp"   // the multivariate-t likelihood's sample moments: this file's tile constants
+#include "mixture_fit.hpp"   // one EM pass of the mixture fit: the mixture kernel's E-step, the moments' reduction

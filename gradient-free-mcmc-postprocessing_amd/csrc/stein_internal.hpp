@@ -164,6 +164,23 @@ struct MvtMomentsArgs {
 };
 int64_t mvt_moments_ws_bytes(int64_t n, int d);                            // host only
 hipError_t launch_mvt_moments(const MvtMomentsArgs& a, hipStream_t s);     // csrc/mvt_moments.hpp (in proxy.hip)
+constexpr int kMixtureEmMaxDim = 16;          // the EM-pass kernel's widest instantiation
+constexpr int kMixtureEmMaxComponents = 32;
+struct MixtureEmArgs {
+    const double* x;         // row-major (n, d) raw sample
+    const double* log_coef;  // (k), means (k, d), P (k, d, d): as MixtureArgs
+    const double* means;
+    const double* P;
+    const double* w;         // (n) row weights >= 0, or NULL: 1
+    int64_t n;
+    int d;
+    int k;
+    double* out;             // LL, then per component N_c, S_c[d], Q_c upper triangle row-major
+    double* log_p;           // (n), or NULL: not written
+    double* ws;              // mixture_em_ws_bytes(n, d, k) bytes: one record per block of grid.x
+};
+int64_t mixture_em_ws_bytes(int64_t n, int d, int k);                      // host only
+hipError_t launch_mixture_em(const MixtureEmArgs& a, hipStream_t s);       // csrc/mixture_fit.hpp (in proxy.hip)
 int dist_tune(int value);    // st_tune key 13 (energy kernel variant)
 
 // the Lotka-Volterra posterior and its RK45 settings, as every LV kernel reads them (csrc/lv_rk45.hpp)

@@ -153,6 +153,9 @@ SIGNATURES = {
     'st_mixture_logpdf_score': (ctypes.c_int, [_c_dp, _i64, _i32, _i32, _c_dp, _c_dp, _c_dp, _c_dp, _c_dp, _c_dp]),
     'st_mvt_moments_workspace_bytes': (_i64, [_i64, _i32]),
     'st_mvt_moments': (ctypes.c_int, [_c_dp, _i64, _i32, _c_dp, _c_dp, _f64, _i32, _c_dp, _c_dp, _i64, _c_dp]),
+    'st_mixture_em_workspace_bytes': (_i64, [_i64, _i32, _i32]),
+    'st_mixture_em_stats': (ctypes.c_int, [_c_dp, _i64, _i32, _i32, _c_dp, _c_dp, _c_dp, _c_dp, _c_dp, _c_dp, _c_dp,
+                                           _i64, _c_dp]),
     # set-batched forms: rows on the device, set_offsets a HOST int64 array (read during the call)
     'st_sets_work_items': (_i64, [_c_dp, _i64, _c_dp, _i64]),
     'st_ksd_sets_workspace_bytes': (_i64, [_i64, _i64, _i32]),

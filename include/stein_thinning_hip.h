@@ -325,6 +325,38 @@ int st_mvt_moments(const double *x, int64_t n, int32_t d, const double *loc, con
                    void *workspace, int64_t workspace_bytes, void *stream);
 
 /* ------------------------------------------------------------------------------------------
+ * One EM pass of a Gaussian-mixture fit (no counterpart in the reference, which never fits a mixture):
+ * the log likelihood of the rows under the current parameters and the sufficient statistics of the
+ * M-step, centred on the CURRENT means.  Parameters as st_mixture_logpdf_score takes them (log_coef,
+ * means, precision, on the DEVICE); row_weights (n, device) non-negative, or NULL for 1.  Per row x_i
+ * and component c, dev_ic = x_i - mu_c, l_ic = a_c - dev_ic . (P_c dev_ic) / 2:
+ *   log_p_i = logsumexp_c l_ic,   r_ic = exp(l_ic - log_p_i)
+ *   LL = sum_i w_i log_p_i,  N_c = sum_i w_i r_ic,  S_c = sum_i w_i r_ic dev_ic (d),
+ *   Q_c = sum_i w_i r_ic dev_ic dev_ic^T (symmetric)
+ * out (device, 1 + k (1 + d + d (d + 1) / 2) doubles): LL, then per component N_c, S_c[d] and the upper
+ * triangle of Q_c row-major.  The M-step is mu_c + S_c / N_c and Q_c / N_c - (S_c / N_c)(S_c / N_c)^T.
+ * log_p_out (n, device) or NULL: log_p_i, bit for bit st_mixture_logpdf_score's log_p (NaN for a row
+ * holding a NaN or an inf).  A component with a_c = -inf is skipped: its statistics are exactly 0.  A row
+ * of weight 0 adds nothing whatever it holds; a non-finite row of positive weight makes LL NaN.
+ * Two launches on `stream` (per-block partial sums into the workspace, then their sum in block order):
+ * no atomics, the same inputs give the same bits on every call at a given grid (the grid follows n, d,
+ * k, the device's CU count and the st_tune grid cap, keys 5 / 23).  Allocates nothing.
+ * workspace: st_mixture_em_workspace_bytes(n, d, k) bytes (host only; -1 if n < 1, d < 1, d > 16, k < 1
+ * or k > 32; bounded by the grid, not by n).
+ * ST_ERR_INVALID: n < 1, d < 1, k < 1, NULL (row_weights and log_p_out may be NULL) or not 8-byte
+ * aligned pointers, a workspace that is too small.  ST_ERR_UNSUPPORTED: d > 16 or k > 32.  All checked
+ * before any HIP call.
+ * ---------------------------------------------------------------------------------------- */
+int64_t st_mixture_em_workspace_bytes(int64_t n, int32_t d, int32_t k);
+int st_mixture_em_stats(const double *x, int64_t n, int32_t d, int32_t k,
+                        const double *log_coef /* k: a_c */, const double *means /* (k, d) */,
+                        const double *precision /* (k, d, d) row-major */,
+                        const double *row_weights /* n, or NULL */,
+                        double *out /* device: LL, then k x {N_c, S_c[d], Q_c upper triangle} */,
+                        double *log_p_out /* n, or NULL */,
+                        void *workspace, int64_t workspace_bytes, void *stream);
+
+/* ------------------------------------------------------------------------------------------
  * KDE proxy -- replaces jax.scipy.stats.gaussian_kde(sample.T, bw_method, weights).logpdf and its
  * jax.grad as the reference's Gaussian-mixture study feeds them to thin_gf (Gaussian_mixture.ipynb
  * cells 42-48, 51).  Whitened data p = x L (n points, SoA (d, ldp)) and queries q = y L (m points,
