@@ -9,6 +9,8 @@
 #include <stdio.h>
 #include <string.h>
 
+#include <initializer_list>
+
 #include "../../include/stein_thinning_hip.h"
 #include "stein_internal.hpp"
 
@@ -458,6 +460,54 @@ int lv_rwmh(hipError_t (*launch)(const st::LvMcmcArgs&, hipStream_t), const char
     if (rc) return rc;
     for (int j = 0; j < 4; ++j) a.step[j] = step_size[j];
     return hip_check(launch(a, static_cast<hipStream_t>(stream)), what);
+}
+
+// the gradient samplers' own checks, after lv_rwmh_args and before any HIP call, and the arguments they share, once:
+// grad, the clip (clip_name, "drift" or "kick", is its name in the messages) and cov_inv.  hw: MALA's h[4] and w[4],
+// a component's checked before its clip.  more: the metric samplers' further device arrays, checked for NULL
+// (more_null) after those three and for 8-byte alignment (more_aligned) after grad's.
+template <class Args>
+int lv_grad_args(Args& a, double* grad, const double* clip, const char* clip_name, const double* cov_inv,
+                 const double* hw = nullptr, std::initializer_list<const void*> more = {},
+                 const char* more_null = nullptr, const char* more_aligned = nullptr) {
+    if (!grad || !clip || !cov_inv) return fail(ST_ERR_INVALID, "NULL pointer (grad, %s_clip, cov_inv)", clip_name);
+    for (const void* m : more)
+        if (!m) return fail(ST_ERR_INVALID, "%s", more_null);
+    if (!aligned16(grad)) return fail(ST_ERR_INVALID, "grad must be 16-byte aligned");
+    for (const void* m : more)
+        if (!aligned8(m)) return fail(ST_ERR_INVALID, "%s", more_aligned);
+    for (int j = 0; j < 4; ++j) {
+        if (hw && !(isfinite(hw[j]) && hw[j] > 0 && isfinite(hw[4 + j]) && hw[4 + j] > 0))
+            return fail(ST_ERR_INVALID, "h and w of component %d must be finite and > 0 (got %g, %g)", j, hw[j],
+                        hw[4 + j]);
+        if (!(clip[j] > 0)) return fail(ST_ERR_INVALID, "%s clip %d must be > 0 (got %g)", clip_name, j, clip[j]);
+        a.clip[j] = clip[j];
+        a.cinv[j] = cov_inv[j];
+    }
+    a.grad = grad;
+    return ST_OK;
+}
+
+// the metric samplers' (st_lv_hmc_metric_wave, st_lv_nuts_wave) own checks and the arguments they share, once:
+// lv_grad_args with `more` = eps_chain, metric_chol and every per-step output, then the sampler's trajectory-length
+// check (length_ok; length_fmt takes `length`), adapt and delta
+template <class Args>
+int lv_metric_args(Args& a, double* grad, const double* kick_clip, const double* cov_inv, const double* eps_chain,
+                   const double* metric_chol, double* accept_stat, double* step_size,
+                   std::initializer_list<const void*> more, const char* more_null, const char* more_aligned,
+                   bool length_ok, const char* length_fmt, int32_t length, int32_t adapt, double delta) {
+    int rc = lv_grad_args(a, grad, kick_clip, "kick", cov_inv, nullptr, more, more_null, more_aligned);
+    if (rc) return rc;
+    if (!length_ok) return fail(ST_ERR_INVALID, length_fmt, (int)length);
+    if (adapt != 0 && adapt != 1) return fail(ST_ERR_INVALID, "adapt must be 0 or 1");
+    if (!(delta > 0 && delta < 1)) return fail(ST_ERR_INVALID, "delta must lie in (0, 1) (got %g)", delta);
+    a.eps_chain = eps_chain;
+    a.metric_chol = metric_chol;
+    a.adapt = adapt;
+    a.delta = delta;
+    a.accept_stat = accept_stat;
+    a.step_size = step_size;
+    return ST_OK;
 }
 
 // st_autocov / st_autocov_workspace_bytes: the shape checks both share (0 ok)
@@ -986,23 +1036,13 @@ int st_lv_mala_wave(double* state, int64_t chains, int64_t first_chain, int64_t 
     int rc = lv_rwmh_args(a, state, chains, first_chain, first_step, steps, init, step_ehw, noise_mode, seed, z,
                           log_u, noise_ld, noise_row0, t_eval, t_n, y_obs, span_u0_tol, whiten, c_log, norm_logc,
                           max_steps, samples, log_p, out_ld, out_row0);
+    if (!rc) rc = lv_grad_args(a, grad, drift_clip, "drift", cov_inv, step_ehw + 4);
     if (rc) return rc;
-    if (!grad || !drift_clip || !cov_inv) return fail(ST_ERR_INVALID, "NULL pointer (grad, drift_clip, cov_inv)");
-    if (!aligned16(grad)) return fail(ST_ERR_INVALID, "grad must be 16-byte aligned");
-    for (int j = 0; j < 4; ++j) {
-        const double h = step_ehw[4 + j], w = step_ehw[8 + j], c = drift_clip[j];
-        if (!isfinite(h) || !(h > 0) || !isfinite(w) || !(w > 0))
-            return fail(ST_ERR_INVALID, "h and w of component %d must be finite and > 0 (got %g, %g)", j, h, w);
-        if (!(c > 0)) return fail(ST_ERR_INVALID, "drift clip %d must be > 0 (got %g)", j, c);
-    }
     for (int j = 0; j < 4; ++j) {
         a.eps[j] = step_ehw[j];
         a.h[j] = step_ehw[4 + j];
         a.w[j] = step_ehw[8 + j];
-        a.clip[j] = drift_clip[j];
-        a.cinv[j] = cov_inv[j];
     }
-    a.grad = grad;
     return hip_check(st::launch_lv_mala_wave(a, static_cast<hipStream_t>(stream)), "lv mala wave launch");
 }
 
@@ -1023,19 +1063,11 @@ int st_lv_hmc_wave(double* state, int64_t chains, int64_t first_chain, int64_t f
     int rc = lv_rwmh_args(a, state, chains, first_chain, first_step, steps, init, step_eps, noise_mode, seed, z,
                           log_u, noise_ld, noise_row0, t_eval, t_n, y_obs, span_u0_tol, whiten, c_log, norm_logc,
                           max_steps, samples, log_p, out_ld, out_row0);
+    if (!rc) rc = lv_grad_args(a, grad, kick_clip, "kick", cov_inv);
     if (rc) return rc;
-    if (!grad || !kick_clip || !cov_inv) return fail(ST_ERR_INVALID, "NULL pointer (grad, kick_clip, cov_inv)");
-    if (!aligned16(grad)) return fail(ST_ERR_INVALID, "grad must be 16-byte aligned");
-    for (int j = 0; j < 4; ++j)
-        if (!(kick_clip[j] > 0)) return fail(ST_ERR_INVALID, "kick clip %d must be > 0 (got %g)", j, kick_clip[j]);
     if (n_leapfrog < 1) return fail(ST_ERR_INVALID, "n_leapfrog must be >= 1 (got %d)", (int)n_leapfrog);
-    for (int j = 0; j < 4; ++j) {
-        a.eps[j] = step_eps[j];
-        a.clip[j] = kick_clip[j];
-        a.cinv[j] = cov_inv[j];
-    }
+    for (int j = 0; j < 4; ++j) a.eps[j] = step_eps[j];
     a.n_leapfrog = n_leapfrog;
-    a.grad = grad;
     return hip_check(st::launch_lv_hmc_wave(a, static_cast<hipStream_t>(stream)), "lv hmc wave launch");
 }
 
@@ -1057,30 +1089,14 @@ int st_lv_hmc_metric_wave(double* state, int64_t chains, int64_t first_chain, in
     int rc = lv_rwmh_args(a, state, chains, first_chain, first_step, steps, init, nullptr, noise_mode, seed, z,
                           log_u, noise_ld, noise_row0, t_eval, t_n, y_obs, span_u0_tol, whiten, c_log, norm_logc,
                           max_steps, samples, log_p, out_ld, out_row0, false);
+    if (!rc)
+        rc = lv_metric_args(a, grad, kick_clip, cov_inv, eps_chain, metric_chol, accept_stat, step_size,
+                            {eps_chain, metric_chol, accept_stat, step_size},
+                            "NULL pointer (eps_chain, metric_chol, accept_stat, step_size)",
+                            "eps_chain, metric_chol, accept_stat and step_size must be 8-byte aligned",
+                            n_leapfrog >= 1, "n_leapfrog must be >= 1 (got %d)", n_leapfrog, adapt, delta);
     if (rc) return rc;
-    if (!grad || !kick_clip || !cov_inv) return fail(ST_ERR_INVALID, "NULL pointer (grad, kick_clip, cov_inv)");
-    if (!eps_chain || !metric_chol || !accept_stat || !step_size)
-        return fail(ST_ERR_INVALID, "NULL pointer (eps_chain, metric_chol, accept_stat, step_size)");
-    if (!aligned16(grad)) return fail(ST_ERR_INVALID, "grad must be 16-byte aligned");
-    if (!aligned8(eps_chain) || !aligned8(metric_chol) || !aligned8(accept_stat) || !aligned8(step_size))
-        return fail(ST_ERR_INVALID, "eps_chain, metric_chol, accept_stat and step_size must be 8-byte aligned");
-    for (int j = 0; j < 4; ++j)
-        if (!(kick_clip[j] > 0)) return fail(ST_ERR_INVALID, "kick clip %d must be > 0 (got %g)", j, kick_clip[j]);
-    if (n_leapfrog < 1) return fail(ST_ERR_INVALID, "n_leapfrog must be >= 1 (got %d)", (int)n_leapfrog);
-    if (adapt != 0 && adapt != 1) return fail(ST_ERR_INVALID, "adapt must be 0 or 1");
-    if (!(delta > 0 && delta < 1)) return fail(ST_ERR_INVALID, "delta must lie in (0, 1) (got %g)", delta);
-    for (int j = 0; j < 4; ++j) {
-        a.clip[j] = kick_clip[j];
-        a.cinv[j] = cov_inv[j];
-    }
-    a.eps_chain = eps_chain;
-    a.metric_chol = metric_chol;
     a.n_leapfrog = n_leapfrog;
-    a.adapt = adapt;
-    a.delta = delta;
-    a.grad = grad;
-    a.accept_stat = accept_stat;
-    a.step_size = step_size;
     return hip_check(st::launch_lv_hmc_metric_wave(a, static_cast<hipStream_t>(stream)), "lv hmc metric wave launch");
 }
 
@@ -1105,32 +1121,15 @@ int st_lv_nuts_wave(double* state, int64_t chains, int64_t first_chain, int64_t 
     if (rc) return rc;
     if (noise_mode == 0)
         return fail(ST_ERR_INVALID, "noise_mode must be 1 or 2: the tree's draws have no supplied-noise form");
-    if (!grad || !kick_clip || !cov_inv) return fail(ST_ERR_INVALID, "NULL pointer (grad, kick_clip, cov_inv)");
-    if (!eps_chain || !metric_chol || !accept_stat || !step_size || !tree_depth || !n_leapfrog || !divergent)
-        return fail(ST_ERR_INVALID, "NULL pointer (eps_chain, metric_chol, accept_stat, step_size, tree_depth, "
-                                    "n_leapfrog, divergent)");
-    if (!aligned16(grad)) return fail(ST_ERR_INVALID, "grad must be 16-byte aligned");
-    if (!aligned8(eps_chain) || !aligned8(metric_chol) || !aligned8(accept_stat) || !aligned8(step_size) ||
-        !aligned8(tree_depth) || !aligned8(n_leapfrog) || !aligned8(divergent))
-        return fail(ST_ERR_INVALID, "eps_chain, metric_chol and the per-step outputs must be 8-byte aligned");
-    for (int j = 0; j < 4; ++j)
-        if (!(kick_clip[j] > 0)) return fail(ST_ERR_INVALID, "kick clip %d must be > 0 (got %g)", j, kick_clip[j]);
-    if (max_depth < 1 || max_depth > 10)
-        return fail(ST_ERR_INVALID, "max_depth must be 1 .. 10 (got %d)", (int)max_depth);
-    if (adapt != 0 && adapt != 1) return fail(ST_ERR_INVALID, "adapt must be 0 or 1");
-    if (!(delta > 0 && delta < 1)) return fail(ST_ERR_INVALID, "delta must lie in (0, 1) (got %g)", delta);
-    for (int j = 0; j < 4; ++j) {
-        a.clip[j] = kick_clip[j];
-        a.cinv[j] = cov_inv[j];
-    }
-    a.eps_chain = eps_chain;
-    a.metric_chol = metric_chol;
+    rc = lv_metric_args(a, grad, kick_clip, cov_inv, eps_chain, metric_chol, accept_stat, step_size,
+                        {eps_chain, metric_chol, accept_stat, step_size, tree_depth, n_leapfrog, divergent},
+                        "NULL pointer (eps_chain, metric_chol, accept_stat, step_size, tree_depth, n_leapfrog, "
+                        "divergent)",
+                        "eps_chain, metric_chol and the per-step outputs must be 8-byte aligned",
+                        max_depth >= 1 && max_depth <= 10, "max_depth must be 1 .. 10 (got %d)", max_depth, adapt,
+                        delta);
+    if (rc) return rc;
     a.max_depth = max_depth;
-    a.adapt = adapt;
-    a.delta = delta;
-    a.grad = grad;
-    a.accept_stat = accept_stat;
-    a.step_size = step_size;
     a.tree_depth = tree_depth;
     a.n_leapfrog = n_leapfrog;
     a.divergent = divergent;

@@ -94,23 +94,70 @@ __device__ inline void device_noise(uint64_t seed, uint64_t chain, uint64_t t, d
     log_u = log((double)(q[0] >> 11) * k2m53);
 }
 
-// DEVICE_NOISE: Philox noise (else a.z / a.log_u are read); RECORD (device noise only): a.z / a.log_u are
-// written.  a.init: the thread first evaluates its start row, stores it as row out_row0 - 1 and takes
-// its density as lp (NaN when that evaluation fails: every later proposal is then rejected and the
-// caller sees the NaN in log_p).
+// ---- the blocks the six kernels share, one copy of each; the loops stay in the kernels ----
+// four doubles at a 16-byte aligned address, as two 16-byte accesses
+__device__ __forceinline__ void load4(const double* src, double v[4]) {
+    const double2 lo = reinterpret_cast<const double2*>(src)[0], hi = reinterpret_cast<const double2*>(src)[1];
+    v[0] = lo.x; v[1] = lo.y; v[2] = hi.x; v[3] = hi.y;
+}
+__device__ __forceinline__ void store4(double* dst, const double v[4]) {
+    reinterpret_cast<double2*>(dst)[0] = make_double2(v[0], v[1]);
+    reinterpret_cast<double2*>(dst)[1] = make_double2(v[2], v[3]);
+}
+
+// the chain's state record: x[4], lp, accepted, n_failed, one spare (8 words); the gradient samplers' records go on
+// with g[4] at word 8 (16 words, read and written by hand in those kernels).  The caller decides which lanes store.
+__device__ __forceinline__ void load_chain8(const double* st, double x[4], double& lp, int64_t& accepted,
+                                            int64_t& failed) {
+    load4(st, x);
+    lp = st[4];
+    accepted = reinterpret_cast<const int64_t*>(st)[5];
+    failed = reinterpret_cast<const int64_t*>(st)[6];
+}
+__device__ __forceinline__ void store_chain8(double* st, const double x[4], double lp, int64_t accepted,
+                                             int64_t failed) {
+    store4(st, x);
+    st[4] = lp;
+    reinterpret_cast<int64_t*>(st)[5] = accepted;
+    reinterpret_cast<int64_t*>(st)[6] = failed;
+}
+
+// row k of the chain's output: the row and its log density
+__device__ __forceinline__ void store_row(double* rows, double* lps, int64_t k, const double x[4], double lp) {
+    store4(rows + 4 * k, x);
+    lps[k] = lp;
+}
+
+// The noise of the step written to row k: z[4] and log_u.  DEVICE_NOISE: Philox noise of global step t (else zs / lus
+// are read); RECORD (device noise only): the `writer` lanes write the values used to zs / lus.
+template <bool DEVICE_NOISE, bool RECORD>
+__device__ __forceinline__ void step_noise(uint64_t seed, uint64_t chain, uint64_t t, double* zs, double* lus,
+                                           int64_t k, bool writer, double z[4], double& log_u) {
+    if constexpr (DEVICE_NOISE) {
+        device_noise(seed, chain, t, z, log_u);
+        if constexpr (RECORD) {
+            if (writer) {
+                store4(zs + 4 * k, z);
+                lus[k] = log_u;
+            }
+        }
+    } else {
+        load4(zs + 4 * k, z);
+        log_u = lus[k];
+    }
+}
+
+// DEVICE_NOISE, RECORD: step_noise's.  a.init: the thread first evaluates its start row, stores it as row
+// out_row0 - 1 and takes its density as lp (NaN when that evaluation fails: every later proposal is then
+// rejected and the caller sees the NaN in log_p).
 template <bool DEVICE_NOISE, bool RECORD>
 __global__ __launch_bounds__(kMcmcThreads) void lv_rwmh_kernel(LvMcmcArgs a) {
     const int64_t i = (int64_t)blockIdx.x * kMcmcThreads + threadIdx.x;
     if (i >= a.chains) return;
     double* st = a.state + 8 * i;
-    int64_t* sti = reinterpret_cast<int64_t*>(st);
     double x[4], lp;
-    {
-        const double2 s0 = reinterpret_cast<const double2*>(st)[0], s1 = reinterpret_cast<const double2*>(st)[1];
-        x[0] = s0.x; x[1] = s0.y; x[2] = s1.x; x[3] = s1.y;
-    }
-    lp = st[4];
-    int64_t accepted = sti[5], failed = sti[6];
+    int64_t accepted, failed;
+    load_chain8(st, x, lp, accepted, failed);
     double* rows = a.samples + (i * a.out_ld + a.out_row0) * 4;
     double* lps = a.log_p + i * a.out_ld + a.out_row0;
     double* zs = nullptr;
@@ -125,21 +172,8 @@ __global__ __launch_bounds__(kMcmcThreads) void lv_rwmh_kernel(LvMcmcArgs a) {
     for (int64_t k = a.init ? -1 : 0; k < a.steps; ++k) {
         const bool start = k < 0;
         double z[4] = {0.0, 0.0, 0.0, 0.0}, log_u = 0.0;
-        if (!start) {
-            if constexpr (DEVICE_NOISE) {
-                device_noise(a.seed, chain, (uint64_t)(a.first_step + k), z, log_u);
-                if constexpr (RECORD) {
-                    reinterpret_cast<double2*>(zs + 4 * k)[0] = make_double2(z[0], z[1]);
-                    reinterpret_cast<double2*>(zs + 4 * k)[1] = make_double2(z[2], z[3]);
-                    lus[k] = log_u;
-                }
-            } else {
-                const double2 z01 = reinterpret_cast<const double2*>(zs + 4 * k)[0];
-                const double2 z23 = reinterpret_cast<const double2*>(zs + 4 * k)[1];
-                z[0] = z01.x; z[1] = z01.y; z[2] = z23.x; z[3] = z23.y;
-                log_u = lus[k];
-            }
-        }
+        if (!start)
+            step_noise<DEVICE_NOISE, RECORD>(a.seed, chain, (uint64_t)(a.first_step + k), zs, lus, k, true, z, log_u);
         double p[4], th[4];
         bool ok = true;
 #pragma unroll
@@ -161,15 +195,9 @@ __global__ __launch_bounds__(kMcmcThreads) void lv_rwmh_kernel(LvMcmcArgs a) {
                 ++accepted;
             }
         }
-        reinterpret_cast<double2*>(rows + 4 * k)[0] = make_double2(x[0], x[1]);
-        reinterpret_cast<double2*>(rows + 4 * k)[1] = make_double2(x[2], x[3]);
-        lps[k] = lp;
+        store_row(rows, lps, k, x, lp);
     }
-    reinterpret_cast<double2*>(st)[0] = make_double2(x[0], x[1]);
-    reinterpret_cast<double2*>(st)[1] = make_double2(x[2], x[3]);
-    st[4] = lp;
-    sti[5] = accepted;
-    sti[6] = failed;
+    store_chain8(st, x, lp, accepted, failed);
 }
 
 // ---- wave layout: one wave (64 lanes) per chain, for a few long chains (file header) ----
@@ -205,14 +233,9 @@ __global__ __launch_bounds__(kWaveLanes * kWaveChainsPerBlock) void lv_rwmh_wave
     const int64_t i = (int64_t)blockIdx.x * kWaveChainsPerBlock + wave;
     if (i >= a.chains) return;            // the whole wave (partial last block)
     double* st = a.state + 8 * i;
-    int64_t* sti = reinterpret_cast<int64_t*>(st);
     double x[4], lp;
-    {
-        const double2 s0 = reinterpret_cast<const double2*>(st)[0], s1 = reinterpret_cast<const double2*>(st)[1];
-        x[0] = s0.x; x[1] = s0.y; x[2] = s1.x; x[3] = s1.y;
-    }
-    lp = st[4];
-    int64_t accepted = sti[5], failed = sti[6];
+    int64_t accepted, failed;
+    load_chain8(st, x, lp, accepted, failed);
     double* rows = a.samples + (i * a.out_ld + a.out_row0) * 4;
     double* lps = a.log_p + i * a.out_ld + a.out_row0;
     double* zs = nullptr;
@@ -226,23 +249,9 @@ __global__ __launch_bounds__(kWaveLanes * kWaveChainsPerBlock) void lv_rwmh_wave
     for (int64_t k = a.init ? -1 : 0; k < a.steps; ++k) {
         const bool start = k < 0;
         double z[4] = {0.0, 0.0, 0.0, 0.0}, log_u = 0.0;
-        if (!start) {
-            if constexpr (DEVICE_NOISE) {
-                device_noise(a.seed, chain, (uint64_t)(a.first_step + k), z, log_u);
-                if constexpr (RECORD) {
-                    if (lane == 0) {
-                        reinterpret_cast<double2*>(zs + 4 * k)[0] = make_double2(z[0], z[1]);
-                        reinterpret_cast<double2*>(zs + 4 * k)[1] = make_double2(z[2], z[3]);
-                        lus[k] = log_u;
-                    }
-                }
-            } else {
-                const double2 z01 = reinterpret_cast<const double2*>(zs + 4 * k)[0];
-                const double2 z23 = reinterpret_cast<const double2*>(zs + 4 * k)[1];
-                z[0] = z01.x; z[1] = z01.y; z[2] = z23.x; z[3] = z23.y;
-                log_u = lus[k];
-            }
-        }
+        if (!start)
+            step_noise<DEVICE_NOISE, RECORD>(a.seed, chain, (uint64_t)(a.first_step + k), zs, lus, k, lane == 0, z,
+                                             log_u);
         double p[4], th[4];
         bool ok = true;
 #pragma unroll
@@ -278,19 +287,9 @@ __global__ __launch_bounds__(kWaveLanes * kWaveChainsPerBlock) void lv_rwmh_wave
                 ++accepted;
             }
         }
-        if (lane == 0) {
-            reinterpret_cast<double2*>(rows + 4 * k)[0] = make_double2(x[0], x[1]);
-            reinterpret_cast<double2*>(rows + 4 * k)[1] = make_double2(x[2], x[3]);
-            lps[k] = lp;
-        }
+        if (lane == 0) store_row(rows, lps, k, x, lp);
     }
-    if (lane == 0) {
-        reinterpret_cast<double2*>(st)[0] = make_double2(x[0], x[1]);
-        reinterpret_cast<double2*>(st)[1] = make_double2(x[2], x[3]);
-        st[4] = lp;
-        sti[5] = accepted;
-        sti[6] = failed;
-    }
+    if (lane == 0) store_chain8(st, x, lp, accepted, failed);
 }
 
 // ---- Metropolis-adjusted Langevin (MALA) sampler, one wave per chain ----
@@ -324,6 +323,10 @@ __device__ __forceinline__ double mala_clip(double v, double c) {
     return v > c ? c : v;
 }
 
+// Written out in each of the four gradient kernels, not helpers (DESIGN.md section 17.1 has the measurements): the
+// 16-word state record and the row stores, K(r), the wave evaluation (lv_integrate<10>, the butterflies, lp_new /
+// g_new), the Lam position update and the accept statistic.  Shared: step_noise above and dual_average below.
+
 template <bool DEVICE_NOISE, bool RECORD>
 __global__ __launch_bounds__(kWaveLanes * kWaveChainsPerBlock) void lv_mala_wave_kernel(LvMalaArgs a) {
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x / kWaveLanes));
@@ -356,23 +359,9 @@ __global__ __launch_bounds__(kWaveLanes * kWaveChainsPerBlock) void lv_mala_wave
     for (int64_t k = a.init ? -1 : 0; k < a.steps; ++k) {
         const bool start = k < 0;
         double z[4] = {0.0, 0.0, 0.0, 0.0}, log_u = 0.0;
-        if (!start) {
-            if constexpr (DEVICE_NOISE) {
-                device_noise(a.seed, chain, (uint64_t)(a.first_step + k), z, log_u);
-                if constexpr (RECORD) {
-                    if (lane == 0) {
-                        reinterpret_cast<double2*>(zs + 4 * k)[0] = make_double2(z[0], z[1]);
-                        reinterpret_cast<double2*>(zs + 4 * k)[1] = make_double2(z[2], z[3]);
-                        lus[k] = log_u;
-                    }
-                }
-            } else {
-                const double2 z01 = reinterpret_cast<const double2*>(zs + 4 * k)[0];
-                const double2 z23 = reinterpret_cast<const double2*>(zs + 4 * k)[1];
-                z[0] = z01.x; z[1] = z01.y; z[2] = z23.x; z[3] = z23.y;
-                log_u = lus[k];
-            }
-        }
+        if (!start)
+            step_noise<DEVICE_NOISE, RECORD>(a.seed, chain, (uint64_t)(a.first_step + k), zs, lus, k, lane == 0, z,
+                                             log_u);
         double d[4], p[4], th[4];
         bool ok = true;
 #pragma unroll
@@ -510,21 +499,8 @@ __global__ __launch_bounds__(kWaveLanes * kWaveChainsPerBlock) void lv_hmc_wave_
     for (int64_t k = a.init ? -1 : 0; k < a.steps;) {
         const bool start = k < 0;
         if (!start && l == 0) {
-            if constexpr (DEVICE_NOISE) {
-                device_noise(a.seed, chain, (uint64_t)(a.first_step + k), r, log_u);
-                if constexpr (RECORD) {
-                    if (lane == 0) {
-                        reinterpret_cast<double2*>(zs + 4 * k)[0] = make_double2(r[0], r[1]);
-                        reinterpret_cast<double2*>(zs + 4 * k)[1] = make_double2(r[2], r[3]);
-                        lus[k] = log_u;
-                    }
-                }
-            } else {
-                const double2 z01 = reinterpret_cast<const double2*>(zs + 4 * k)[0];
-                const double2 z23 = reinterpret_cast<const double2*>(zs + 4 * k)[1];
-                r[0] = z01.x; r[1] = z01.y; r[2] = z23.x; r[3] = z23.y;
-                log_u = lus[k];
-            }
+            step_noise<DEVICE_NOISE, RECORD>(a.seed, chain, (uint64_t)(a.first_step + k), zs, lus, k, lane == 0, r,
+                                             log_u);
             double s = 0.0;
 #pragma unroll
             for (int j = 0; j < 4; ++j) s += r[j] * r[j];
@@ -627,9 +603,10 @@ __global__ __launch_bounds__(kWaveLanes * kWaveChainsPerBlock) void lv_hmc_wave_
 // read again in every stage (uniform loads), not kept across the integration.
 // (2) per step, a.accept_stat = alpha = min(1, exp(a)), a = (lp(q^L) - lp(x)) + (K(r^0) - K(r^L)), 0 when a is NaN, and
 // a.step_size = the eps the step used (rows out_row0 + k of (chains, out_ld) arrays; the start row has none).
-// (3) a.adapt = 1: eps comes from the state record and follows Stan's dual averaging after every step (delta handed
-// over, gamma 0.05, t0 10, kappa 0.75):  m <- m + 1;  eta = 1 / (m + t0);  sbar <- (1 - eta) sbar + eta (delta - alpha);
-// ell = mu - (sbar sqrt(m)) / gamma;  w = pow(m, -kappa);  xbar <- (1 - w) xbar + w ell;  eps <- exp(ell).
+// (3) a.adapt = 1: eps comes from the state record and follows Stan's dual averaging after every step (dual_average;
+// delta handed over, gamma 0.05, t0 10, kappa 0.75):  m <- m + 1;  eta = 1 / (m + t0);
+// sbar <- (1 - eta) sbar + eta (delta - alpha);  ell = mu - (sbar sqrt(m)) / gamma;  w = pow(m, -kappa);
+// xbar <- (1 - w) xbar + w ell;  eps <- exp(ell).
 // The state record has 24 words per chain: LvMalaArgs' 16, then eps, m, sbar, xbar, mu and three spare.  The five are
 // loaded and stored at the step's end -- only eps is live across the integration -- by EVERY lane (the same bits to the
 // same address), so that each lane reads back what it wrote itself.  With a.adapt = 0 they are neither read nor
@@ -647,6 +624,22 @@ __device__ __forceinline__ void metric_half_kick(const double* lam, const double
         for (int k = j + 1; k < 4; ++k) f += lam[k * (k + 1) / 2 + j] * g[k];
         hk[j] = 0.5 * mala_clip(eps * f, c[j]);
     }
+}
+
+// One step of the dual averaging (3) on the record's words 16 .. 20 (eps, m, sbar, xbar, mu); returns the new eps.
+// Called by EVERY lane: each stores the same bits to the same address and reads back what it wrote itself.
+__device__ __forceinline__ double dual_average(double* st, double delta, double alpha) {
+    const double m = st[17] + 1.0, eta = 1.0 / (m + kDaT0);
+    const double sbar = (1.0 - eta) * st[18] + eta * (delta - alpha);
+    const double ell = st[20] - (sbar * sqrt(m)) / kDaGamma;
+    const double w = pow(m, -kDaKappa);
+    const double xbar = (1.0 - w) * st[19] + w * ell;
+    const double eps = exp(ell);
+    st[16] = eps;
+    st[17] = m;
+    st[18] = sbar;
+    st[19] = xbar;
+    return eps;
 }
 
 template <bool DEVICE_NOISE, bool RECORD>
@@ -690,21 +683,8 @@ __global__ __launch_bounds__(kWaveLanes * kWaveChainsPerBlock) void lv_hmc_metri
     for (int64_t k = a.init ? -1 : 0; k < a.steps;) {
         const bool start = k < 0;
         if (!start && l == 0) {
-            if constexpr (DEVICE_NOISE) {
-                device_noise(a.seed, chain, (uint64_t)(a.first_step + k), r, log_u);
-                if constexpr (RECORD) {
-                    if (lane == 0) {
-                        reinterpret_cast<double2*>(zs + 4 * k)[0] = make_double2(r[0], r[1]);
-                        reinterpret_cast<double2*>(zs + 4 * k)[1] = make_double2(r[2], r[3]);
-                        lus[k] = log_u;
-                    }
-                }
-            } else {
-                const double2 z01 = reinterpret_cast<const double2*>(zs + 4 * k)[0];
-                const double2 z23 = reinterpret_cast<const double2*>(zs + 4 * k)[1];
-                r[0] = z01.x; r[1] = z01.y; r[2] = z23.x; r[3] = z23.y;
-                log_u = lus[k];
-            }
+            step_noise<DEVICE_NOISE, RECORD>(a.seed, chain, (uint64_t)(a.first_step + k), zs, lus, k, lane == 0, r,
+                                             log_u);
             double s = 0.0;
 #pragma unroll
             for (int j = 0; j < 4; ++j) s += r[j] * r[j];
@@ -789,18 +769,7 @@ __global__ __launch_bounds__(kWaveLanes * kWaveChainsPerBlock) void lv_hmc_metri
                 alphas[k] = alpha;
                 epss[k] = eps;
             }
-            if (a.adapt) {
-                const double m = st[17] + 1.0, eta = 1.0 / (m + kDaT0);
-                const double sbar = (1.0 - eta) * st[18] + eta * (a.delta - alpha);
-                const double ell = st[20] - (sbar * sqrt(m)) / kDaGamma;
-                const double w = pow(m, -kDaKappa);
-                const double xbar = (1.0 - w) * st[19] + w * ell;
-                eps = exp(ell);
-                st[16] = eps;             // every lane: the same bits (above)
-                st[17] = m;
-                st[18] = sbar;
-                st[19] = xbar;
-            }
+            if (a.adapt) eps = dual_average(st, a.delta, alpha);
         }
         if (lane == 0) {
             reinterpret_cast<double2*>(rows + 4 * k)[0] = make_double2(x[0], x[1]);
@@ -924,10 +893,7 @@ __global__ __launch_bounds__(kWaveLanes * kWaveChainsPerBlock) void lv_nuts_wave
                 double unused;
                 device_noise(a.seed, chain, t, r, unused);
                 if constexpr (RECORD) {
-                    if (lane == 0) {
-                        reinterpret_cast<double2*>(zs + 4 * k)[0] = make_double2(r[0], r[1]);
-                        reinterpret_cast<double2*>(zs + 4 * k)[1] = make_double2(r[2], r[3]);
-                    }
+                    if (lane == 0) store4(zs + 4 * k, r);
                 }
                 double s = 0.0;
 #pragma unroll
@@ -1104,18 +1070,7 @@ __global__ __launch_bounds__(kWaveLanes * kWaveChainsPerBlock) void lv_nuts_wave
                 a.n_leapfrog[row0 + k] = (double)l;
                 a.divergent[row0 + k] = divergent ? 1.0 : 0.0;
             }
-            if (a.adapt) {                // lv_hmc_metric_wave_kernel's recurrence
-                const double m = st[17] + 1.0, eta = 1.0 / (m + kDaT0);
-                const double sbar = (1.0 - eta) * st[18] + eta * (a.delta - alpha);
-                const double ell = st[20] - (sbar * sqrt(m)) / kDaGamma;
-                const double w = pow(m, -kDaKappa);
-                const double xbar = (1.0 - w) * st[19] + w * ell;
-                eps = exp(ell);
-                st[16] = eps;             // every lane: the same bits
-                st[17] = m;
-                st[18] = sbar;
-                st[19] = xbar;
-            }
+            if (a.adapt) eps = dual_average(st, a.delta, alpha);
         }
         // the row: the proposal
 #pragma unroll
